@@ -18,6 +18,11 @@ to consumers, delivery tags, Basic.Deliver rendering into host-mapped egress mem
 auto-ack release — nothing skipped.
 
 python bench.py [--gpus N --steps K --warmup W]   (N>1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step delivered (``dump_outputs``).
+``--full`` adds what the headline figure does not need: two more steps whose egress is
+parsed and checked (``verify_egress``) and the untimed soak after the result line.
 """
 
 import argparse
@@ -149,6 +154,62 @@ def verify_egress(dp, base, pool_len, tickets):
     return checked
 
 
+DUMP_SAMPLE = 4 << 20   # elements of egress_wire.npy (16 MB as float32)
+
+
+def dump_outputs(dp, ticket, out_dir, rank=0, world=1):
+    """What the consumers of the timed path received in its last step, as ``.npy`` arrays
+    that two builds can be compared by.  The interleaving ACROSS publishers within a step
+    is unordered by design (AMQP orders per channel only), so the step's commands are put
+    in a canonical order first: per connection, sorted by their bytes with the delivery tag
+    (their position in the step) zeroed.  The files therefore compare WHAT every consumer
+    received in the step and how much, not the order within a consumer connection: a
+    delivered message does not name its publisher, so the per-publisher order that AMQP
+    guarantees is not in them (tests/test_gpu_scale.py checks it, with bodies that do).
+
+    deliveries.npy   float64 [n, 4]: connection, channel, bytes, CRC-32 of every command
+                     (method payload with tag 0 + content header properties + body)
+    delivery_tags.npy float64 [connections, 3]: connection, first and last delivery tag
+    egress_wire.npy  float32: the canonical command bytes, all of them up to DUMP_SAMPLE
+                     elements, else a fixed seeded sample of that many positions
+    counters.npy     float64 [3]: publishes decoded, deliveries rendered, wire bytes"""
+    import zlib
+
+    from chanamq_amd.protocol.codec import CommandAssembler, FrameParser
+    eg, co = dp.host_egress(ticket)
+    c = dp.eng.counters(ticket[0])
+    rows, tags, blobs = [], [], []
+    wire_bytes = 0
+    for conn in np.nonzero(co["len"])[0]:
+        o, n = int(co["off"][conn]), int(co["len"][conn])
+        wire_bytes += n
+        fp, ca = FrameParser(), CommandAssembler()
+        mine, seen = [], []
+        for f in fp.feed(bytes(eg[o:o + n])):
+            cmd = ca.feed(f)
+            if cmd is None or cmd.method is None:
+                continue
+            if "delivery_tag" in cmd.method.args:
+                seen.append(int(cmd.method.args["delivery_tag"]))
+                cmd.method.args["delivery_tag"] = 0
+            mine.append((cmd.channel, cmd.method.encode_payload() + (cmd.raw_header or b"") + bytes(cmd.body)))
+        mine.sort()
+        rows += [(int(conn), ch, len(b), zlib.crc32(b)) for ch, b in mine]
+        blobs += [b for _, b in mine]
+        if seen:
+            tags.append((int(conn), seen[0], seen[-1]))
+    flat = np.frombuffer(b"".join(blobs), np.uint8)
+    if len(flat) > DUMP_SAMPLE:
+        flat = flat[np.sort(np.random.default_rng(0).choice(len(flat), DUMP_SAMPLE, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, arr in (("deliveries", np.array(rows, np.float64).reshape(-1, 4)),
+                      ("delivery_tags", np.array(tags, np.float64).reshape(-1, 3)),
+                      ("egress_wire", flat.astype(np.float32)),
+                      ("counters", np.array([c["n_pubs"], c["n_deliv"], wire_bytes], np.float64))):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
+
+
 def setup_native_exchange(args, cfg, GpuDataPlane, dist, backend, local, rank, world):
     """The sharded plane on the engine's native exchange, as the sharded server builds it
     (server/sharded.py): rank 0 draws the RCCL unique id and names the shared-memory
@@ -186,7 +247,8 @@ def setup_native_exchange(args, cfg, GpuDataPlane, dist, backend, local, rank, w
     return dp
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, with the defaults that depend on ``--full`` filled in."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -199,9 +261,16 @@ def main():
                          "(65536: ~38 M at p50 1.08 ms, but box-to-box outliers; 32768: ~30 M at 0.73 ms; "
                          "profiles/r4_summary.md)")
     ap.add_argument("--blocks", type=int, default=8)
-    ap.add_argument("--soak-s", type=float, default=2.0,
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: two more steps whose egress is parsed and "
+                         "checked (egress_ref.verified in the result line), and the untimed soak (--soak-s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step delivered as DIR/<name>.npy "
+                         "(dump_outputs; the inputs are seeded: the same arguments give the same arrays)")
+    ap.add_argument("--soak-s", type=float, default=None,
                     help="after the timed steps (and the result line), keep stepping untimed for this long so "
-                         "an external GPU-utilisation sampler sees the workload (0 = off)")
+                         "an external GPU-utilisation sampler sees the workload (default: 2.0 with --full, "
+                         "else 0 = off)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--overlap", type=int, default=0, choices=[0, 1],
                     help="1: a step's ingest half on its own high-priority stream (it may run beside the "
@@ -267,7 +336,16 @@ def main():
     ap.add_argument("--async-x", type=int, default=0,
                     help="1: native exchange on the engine's exchange thread, phase B waiting on the device "
                          "(default 0: the stepper runs each exchange itself; profiles/r5_summary.md)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.soak_s is None:
+        args.soak_s = 2.0 if args.full else 0.0
+    # the checked extra steps: only behind --full (and only with egress by reference)
+    args.verify_steps = 2 if args.full and args.egress_ref else 0
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:   # lockstep exchange steps: the blocking loop (every rank submits in step)
@@ -344,6 +422,7 @@ def main():
     pre = set()     # steps whose payload H2D is already queued (prefetch)
     lat_w = []      # (publish->deliver seconds, deliveries) of the timed steps
     wire, nref = [0], [0]
+    last_tk = [None]   # ticket of the last step submitted (--dump-outputs)
 
     def run(n, measure=False):
         # software pipeline, 3 steps in flight: H2D(t+1) || kernels(t) || D2H(t-1);
@@ -405,6 +484,7 @@ def main():
             else:
                 sg = segs[b]
             t = submit(sg, base + offs[b], blens[b])
+            last_tk[0] = t
             s = step_i
             step_i += 1
             nxt = max(step_i, max(pre) + 1 if pre else step_i)
@@ -512,6 +592,8 @@ def main():
                 phases.append(ph)
                 if sum(ph) > slow["ms"]:
                     slow.update(ms=round(sum(ph), 3), step=i, phases_ms=ph)
+        if pending:
+            last_tk[0] = pending[-1][0]
         for t, s in waited:
             account(dp.finish(t, collect=False, wait_egress=False, waited=True), s)
             done.append((t, s))
@@ -546,10 +628,12 @@ def main():
         dist.barrier()
     t = time.perf_counter() - t0
     n_ref_timed, wire_timed = nref[0], wire[0]
+    if args.dump_outputs and last_tk[0] is not None:   # the last timed step: nothing submitted since
+        dump_outputs(dp, last_tk[0], args.dump_outputs, rank, world)
     verified = None
-    if args.egress_ref:   # two more steps, each finished and checked on its own (every rank)
+    if args.verify_steps:   # two more steps, each finished and checked on its own (every rank)
         verified = 0
-        for _ in range(2):
+        for _ in range(args.verify_steps):
             b = step_i % args.blocks
             tk = submit(segs[b], base + offs[b], blens[b])
             step_i += 1
@@ -655,6 +739,7 @@ def main():
             "async_exchange": bool(args.async_x) if shards > 1 else None,
             "prefetch": bool(args.prefetch), "parities": npar, "h2d_alt": bool(args.h2d_alt), "h2d_hsa": bool(args.h2d_hsa), "h2d_at_wait": bool(args.h2d_at_wait),
             "chunk_bytes_per_producer": args.chunk,
+            "full": bool(args.full),
             "post_soak_s": args.soak_s,
         }
         print(json.dumps(out), flush=True)
