@@ -351,14 +351,11 @@ DEV bool topic_match(const u8* pat, u32 plen, const u8* key, u32 klen, bool hash
 
 // ============================================================================ deferred control writes
 // The control plane's table writes (connection / channel / consumer state) staged while
-// steps run, packed per step by the host (Engine::pack_deltas): applied by k_stage before
-// the step reads anything, so no pipeline drain is needed for them.  Layout:
+// steps run, packed per step by the host (DeltaStage::pack_deltas): applied by k_stage before
+// the step reads anything, so no pipeline drain is needed for them.  Layout (step_abi.h):
 //   DeltaHead | DeltaRec[nrec] | u32 dirty channel slots[ndirty] (16-B padded) | data chunks
 // Records never overlap (the host keeps the last write of every byte), so they are applied
 // in parallel: 16-byte chunk i belongs to record r with chunk0[r] <= i < chunk0[r + 1].
-struct DeltaHead { u32 nrec, ndirty, nchunk, pad; };
-struct DeltaRec { u64 dst; u32 len; u32 chunk0; };
-#define DELTA_REC_MAX 1024   // records per step (the host keeps the rest for later steps)
 DEV void apply_deltas(const DS& d, const u8* buf, u32 tid, u32 nt, DeltaRec* lrec) {
   const DeltaHead h = *(const DeltaHead*)buf;
   const DeltaRec* recs = (const DeltaRec*)(buf + sizeof(DeltaHead));

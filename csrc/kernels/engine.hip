@@ -9,13 +9,13 @@
 
 #include <chrono>
 #include <algorithm>
-#include <deque>
 #include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <condition_variable>
 #include <thread>
+#include <type_traits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -26,6 +26,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "dataplane.hip"
+#include "delta_stage.h"
 #include "xchg_host.h"
 #include "xchg_rccl.h"
 
@@ -68,6 +69,81 @@ struct Buf {
 // host then submits step t+1 once step t-2 -- not t-1 -- is collected, so the next step's
 // ingress H2D never waits for the host to notice the previous step's kernels ending
 static constexpr int NPAR_MAX = 3;
+
+// a parity's device view (what its kernels get) + host addresses of its mapped outputs
+struct HostIO : DS {
+  const Counters* ctr_host_h = nullptr;
+  const SegOut* seg_out_hh = nullptr;
+  const ConnOut* conn_out_hh = nullptr;
+  const CtrlRec* ctrl_rec_hh = nullptr;
+  const u8* ctrl_hh = nullptr;
+  const RingMove* grow_hh = nullptr;
+  const u32* conn_conf_hh = nullptr;
+  GetOut* get_out_hh = nullptr;
+  u32* xchg_h = nullptr;   // the exchange words (XC_*): send counts out, receive counts in
+};
+
+// one parity: the step IO set, the staging buffers its submit fills, where its step stands
+struct StepSlot {
+  HostIO io;
+  // host-mapped staging read by k_stage / copied H2D with the step
+  StepIn* stage_in = nullptr;
+  SegIn* stage_segs = nullptr;
+  GetReq* stage_gets = nullptr;
+  u32* stage_unp = nullptr;
+  u8* dl_h = nullptr;              // delta buffer (DeltaStage::pack_deltas)
+  // the submitted step
+  bool inflight = false;           // submitted, results not collected
+  bool staged = false;             // submitted with defer, kernels not launched yet
+  u64 launch_seq = 0;              // its step number
+  int slot = 0, pslot = 0;         // its egress slot / store-record slot
+  u32 nget = 0, nunp = 0;          // Basic.Gets / unpauses it carried
+  u32 dl_step = 0;                 // delta bytes it carried
+  bool h2d_hip = true;             // its stream waits for ev_h2d
+  u64 h2d_addr = 0, h2d_addr2 = 0; // the words its k_h2d_wait polled (0: none; second half of a split payload)
+  bool eager_d2h = false;          // its egress copy was queued at launch (copy_mode 2)
+  // a payload queued ahead of its submit (prefetch)
+  bool pre = false;
+  u64 pre_seq = 0, pre_ptr = 0, pre_len = 0;
+  // overlapped halves recorded at least once
+  bool rest_issued = false;
+  // sharded steps
+  bool phase_a = false;            // phase A launched, submit_b due
+  bool counts_ready = false;       // phase A launched, send counts not yet taken
+  bool b_due = false;              // phase A launched, launch_b due (native exchange)
+  u32 b_wait = 0;                  // the exchange job its phase B waits for (0: none)
+  u8 *xs_desc = nullptr, *xs_pay = nullptr, *xr_desc = nullptr, *xr_pay = nullptr;   // native exchange
+  u8 *ls_desc = nullptr, *ls_pay = nullptr, *lk_send = nullptr, *rack = nullptr;     // links
+  // graphs, captured on first use: whole step / phase A, phase B, overlapped ingest + rest
+  hipGraphExec_t graph_exec = nullptr, graph_b = nullptr, graph_ing = nullptr, graph_rest = nullptr;
+  // H2D queued, step finished, phase A finished, external exchange stream, ingest half,
+  // payload stream, routing half
+  hipEvent_t ev_h2d, ev_done, ev_a, ev_ext, ev_ing, ev_pre, ev_rest;
+};
+
+// egress slots rotate per step (step t renders into slot t % EGRESS_SLOTS)
+struct EgressSlot {
+  u8* dev = nullptr;               // rendered on the device
+  u8* host = nullptr;              // D2H target
+  u8* host_dev = nullptr;          // its device address (copy_mode 2: the copy kernel stores into it)
+  hipEvent_t ev_d2h;
+  bool d2h_issued = false;
+  // HSA SDMA egress: completion of the bulk copy and of the host-issued tail, the gate the
+  // step's last kernel opens, bytes copied speculatively behind the gate (0: not gated)
+  hsa_signal_t sdma_sig{}, tail_sig{}, gate_sig{};
+  bool sdma_pending = false, tail_pending = false;
+  u64 spec = 0;
+};
+
+// ingress payload slots rotate per step (StepIn.ingress)
+struct IngressSlot {
+  u8* buf = nullptr;
+  hipEvent_t ev_read;              // its last reader (the step's routing half)
+  bool read_issued = false;
+  // HSA ingress (cfg h2d_hsa): completion of the payload copy, of a split payload's second half
+  hsa_signal_t sig{}, sig2{};
+  bool hsa = false, split = false; // the slot's last payload went through HSA / in two halves
+};
 
 class Engine {
  public:
@@ -228,68 +304,22 @@ class Engine {
       d_.work = (u8*)view("work", base, d_.work_cap + 4096);   // imports are read in place (k_import_route)
       work_p1_ = (u8*)view("work_p1", base + wb, d_.work_cap + 4096);
       for (int k = 0; k < INGRESS_SLOTS; ++k)
-        ingress_slot_[k] = (u8*)view(("ingress_s" + std::to_string(k)).c_str(), base + 2 * wb + k * ib, d_.ingress_cap + 64);
+        ing_[k].buf = (u8*)view(("ingress_s" + std::to_string(k)).c_str(), base + 2 * wb + k * ib, d_.ingress_cap + 64);
     }
     // per-parity step IO: step t uses set t % npar_, so step t+1's H2D and step t-1's D2H
     // overlap step t's kernels (the graph of each parity is captured once)
     npar_ = (d_.world == 1 && get("overlap", 1) == 0 && get("parities", 2) >= 3) ? 3 : 2;
-    for (int p = 0; p < npar_; ++p) {
-      std::string sfx = std::to_string(p);
-      DS& io = io_[p];
-      io.in = (StepIn*)dev(("in" + sfx).c_str(), sizeof(StepIn));
-      io.segs = (const SegIn*)dev(("segs" + sfx).c_str(), sizeof(SegIn) * d_.seg_max);
-      // ingress payloads rotate over INGRESS_SLOTS buffers by step (StepIn.ingress): the
-      // next step's payload goes into a slot whose last reader (three steps back) is known
-      // done, so an early H2D never waits on the GPU
-      io.ingress = ingress_slot_[p];
-      io.seg_out = (SegOut*)dev(("seg_out_d" + sfx).c_str(), sizeof(SegOut) * d_.seg_max);
-      io.seg_out_h = (SegOut*)hst(("seg_out" + sfx).c_str(), sizeof(SegOut) * d_.seg_max);
-      io.ctr_host = (Counters*)hst(("ctr_host" + sfx).c_str(), sizeof(Counters));
-      io.conn_out = (ConnOut*)dev(("conn_out_d" + sfx).c_str(), sizeof(ConnOut) * d_.c_max);
-      io.conn_out_h = (ConnOut*)hst(("conn_out" + sfx).c_str(), sizeof(ConnOut) * d_.c_max);
-      io.ctrl = (u8*)dev(("ctrl_d" + sfx).c_str(), d_.ctrl_cap);
-      io.ctrl_h = (u8*)hst(("ctrl" + sfx).c_str(), d_.ctrl_cap);
-      io.ctrl_rec = (CtrlRec*)dev(("ctrl_rec_d" + sfx).c_str(), sizeof(CtrlRec) * d_.seg_max * 2);
-      io.ctrl_rec_h = (CtrlRec*)hst(("ctrl_rec" + sfx).c_str(), sizeof(CtrlRec) * d_.seg_max * 2);
-      io.grow_h = (RingMove*)hst(("grow" + sfx).c_str(), sizeof(RingMove) * GROW_MAX);
-      io.conn_conf_h = (u32*)hst(("conn_conf" + sfx).c_str(), 4ull * d_.c_max);
-      io.xchg = (u32*)hst(("xchg" + sfx).c_str(), 4ull * XC_WORDS);
-      if (d_.persist && p == 0)
-        for (int k = 0; k < PSLOTS; ++k) {   // shared by both parities (rotating per step)
-          const std::string ks = std::to_string(k);
-          d_.ps_persist[k] = (u8*)hst(("persist" + ks).c_str(), d_.persist_bytes + 64);
-          d_.ps_crec[k] = (ConsumedRec*)hst(("consumed" + ks).c_str(), sizeof(ConsumedRec) * (u64)d_.persist_max + 64);
-        }
-      // the step's descriptors stay in host-mapped memory: k_stage reads them over PCIe
-      // and writes the device copies (io.in / io.segs) the later kernels read.  Two H2D
-      // copies per step were runtime blit kernels on a third hardware queue, ordered behind
-      // the prefetched payload: ~50 us between the payload's arrival and the ingest
-      io.in_h = (const StepIn*)hst(("stage_in" + sfx).c_str(), sizeof(StepIn));
-      io.segs_h = (const SegIn*)hst(("stage_segs" + sfx).c_str(), sizeof(SegIn) * d_.seg_max + 64);
-      stage_in_[p] = (StepIn*)buf("stage_in" + sfx).ptr;
-      stage_segs_[p] = (SegIn*)buf("stage_segs" + sfx).ptr;
-      // deferred control writes ridden by this parity's steps (pack_deltas)
-      io.delta_h = (const u8*)hst(("delta" + sfx).c_str(), DELTA_CAP);
-      dl_h_[p] = (u8*)buf("delta" + sfx).ptr;
-      // Basic.Get on the step: the requests (H2D with the step) and their answers
-      io.get_req = (const GetReq*)dev(("get_req" + sfx).c_str(), sizeof(GetReq) * GET_STEP_MAX);
-      io.get_out_h = (GetOut*)hst(("get_out" + sfx).c_str(), sizeof(GetOut) * GET_STEP_MAX);
-      stage_gets_[p] = (GetReq*)pinned(("stage_gets" + sfx).c_str(), sizeof(GetReq) * GET_STEP_MAX);
-      io.unpause_req = (const u32*)dev(("unpause_req" + sfx).c_str(), 4ull * UNPAUSE_STEP_MAX);
-      stage_unp_[p] = (u32*)pinned(("stage_unp" + sfx).c_str(), 4ull * UNPAUSE_STEP_MAX);
-    }
-
     // egress slots rotate per step independently of the IO parity: step t renders into
     // slot t % EGRESS_SLOTS, so its kernels only wait for the D2H of step t-3 (long done)
     // instead of step t-2's, which is still on the copy engine
     for (int e = 0; e < EGRESS_SLOTS; ++e) {
       std::string sfx = std::to_string(e);
-      egress_dev_[e] = (u8*)dev(("egress" + sfx).c_str(), egress_alloc_);
+      EgressSlot& es = eg_[e];
+      es.dev = (u8*)dev(("egress" + sfx).c_str(), egress_alloc_);
       if (copy_mode_ == 2) {
-        egress_host_dev_[e] = (u8*)hst(("egress_host" + sfx).c_str(), egress_alloc_);
-        egress_host_[e] = (u8*)buf("egress_host" + sfx).ptr;
+        es.host = (u8*)mapped(&es.host_dev, "egress_host" + sfx, egress_alloc_);
       } else {
-        egress_host_[e] = (u8*)pinned(("egress_host" + sfx).c_str(), egress_alloc_);
+        es.host = (u8*)pinned(("egress_host" + sfx).c_str(), egress_alloc_);
       }
     }
     d_.carry = (u8*)dev("carry", (u64)d_.c_max * d_.carry_cap + 64);
@@ -303,7 +333,7 @@ class Engine {
     d_.conn_conf_bytes = (u32*)dev("conn_conf_bytes", 4ull * d_.c_max);
     d_.conn_dfirst = (u32*)dev("conn_dfirst", 4ull * d_.c_max);
     d_.conn_dlast = (u32*)dev("conn_dlast", 4ull * d_.c_max);
-    d_.conn_wblock = (const u32*)hst("conn_wblock", 4ull * d_.c_max);
+    wblock_h_ = (u32*)mapped(&d_.conn_wblock, "conn_wblock", 4ull * d_.c_max);
     d_.conn_total = (u32*)dev("conn_total", 4ull * d_.c_max);
     d_.conn_base = (u32*)dev("conn_base", 4ull * d_.c_max);
 
@@ -533,8 +563,8 @@ class Engine {
     // Basic.Get: rendered frames + result, host-mapped (a stored body never exceeds the
     // carry, which bounds an assembled command)
     get_cap_ = (u64)d_.carry_cap + d_.carry_cap / 64 + 4096;
-    get_out_dev_ = (u8*)hst("get_out", get_cap_);
-    get_res_dev_ = (GetRes*)hst("get_res", sizeof(GetRes));
+    get_out_h_ = (u8*)mapped(&get_out_dev_, "get_out", get_cap_);
+    get_res_h_ = (GetRes*)mapped(&get_res_dev_, "get_res", sizeof(GetRes));
     // k_frame_scan phase timestamps (scripts/frame_scan_phases.py): off unless asked for --
     // each mark is a clock read plus a store on the block's critical path
     d_.dbg = get("fs_marks", 0) ? (u64*)dev("dbg", 8ull * 16 * d_.seg_max) : nullptr;
@@ -562,74 +592,103 @@ class Engine {
     dup(&DS::pub_kwoff, "pub_kwoff", 2ull * TOPIC_WORDS * d_.pub_cap + 64);
     dup(&DS::acks, "acks", sizeof(Ack) * (u64)d_.ack_max);
     dup(&DS::dget, "dget", sizeof(DGet) * (u64)DGET_MAX);
-    for (int p = 0; p < npar_; ++p) {
-      DS io = d_;
-      if (p == 1)
-        for (auto& f : par1_) f(io);
-      io.in = io_[p].in; io.segs = io_[p].segs; io.ingress = io_[p].ingress; io.seg_out = io_[p].seg_out;
-      io.ctr_host = io_[p].ctr_host; io.conn_out = io_[p].conn_out;
-      io.ctrl = io_[p].ctrl; io.ctrl_rec = io_[p].ctrl_rec; io.xchg = io_[p].xchg;
-      io.seg_out_h = io_[p].seg_out_h; io.conn_out_h = io_[p].conn_out_h; io.ctrl_h = io_[p].ctrl_h;
-      io.ctrl_rec_h = io_[p].ctrl_rec_h; io.grow_h = io_[p].grow_h; io.conn_conf_h = io_[p].conn_conf_h;
-      io.get_req = io_[p].get_req; io.get_out_h = io_[p].get_out_h; io.unpause_req = io_[p].unpause_req;
-      io.in_h = io_[p].in_h; io.segs_h = io_[p].segs_h; io.delta_h = io_[p].delta_h;
-      static_cast<DS&>(io_[p]) = io;
-    }
     // native exchange (sharded steps driven by the native front end, csrc/core/frontend.cpp):
     // the engine owns the per-parity send / receive buffers and moves them itself (RCCL or
     // the host shared-memory backend); implies the pipelined (lagged) exchange
     native_x_ = d_.world > 1 && get("native_xchg", 0) != 0;
-    if (native_x_) {
-      lag_ = true;
-      for (int p = 0; p < 2; ++p) {
-        std::string sfx = std::to_string(p);
-        xs_desc_[p] = (u8*)dev(("xs_desc" + sfx).c_str(), 64ull * d_.xfer_desc_max + 64);
-        xs_pay_[p] = (u8*)dev(("xs_pay" + sfx).c_str(), d_.xfer_bytes + 64);
-        xr_desc_[p] = (u8*)dev(("xr_desc" + sfx).c_str(), 64ull * d_.import_max + 64);
-        xr_pay_[p] = (u8*)dev(("xr_pay" + sfx).c_str(), d_.import_bytes + 64);
-      }
-      for (int p = 0; p < 2; ++p) {   // parity p packs into S[p], imports R[p^1]
-        io_[p].send_desc = (RDesc*)xs_desc_[p]; io_[p].send_pay = xs_pay_[p];
-        io_[p].recv_desc = (const RDesc*)xr_desc_[p ^ 1]; io_[p].recv_pay = xr_pay_[p ^ 1];
-      }
-      xfer_set_ = true;
-    }
+    if (native_x_) lag_ = xfer_set_ = true;
     if (links_) {
-      DS& L = d_;
-      L.links = 1;
-      L.lk_cap = (u32)get("link_acks", 2ull * d_.deliv_max);
-      L.conn_link = (u32*)dev("conn_link", 4ull * d_.c_max);
-      L.conn_link_tq = (u32*)dev("conn_link_tq", 4ull * d_.c_max);
-      L.conn_link_epoch = (u32*)dev("conn_link_epoch", 4ull * d_.c_max);
-      L.link_conns = (u32*)dev("link_conns", 4ull * 64);
-      L.n_link_conns = (u32*)dev("n_link_conns", 4);
-      L.link_nbase = (u32*)dev("link_nbase", 4ull * d_.c_max);
-      L.link_bbase = (u32*)dev("link_bbase", 4ull * d_.c_max);
-      L.link_dbase = (u32*)dev("link_dbase", 4ull * WORLD_MAX);
-      L.q_link_owner = (u32*)dev("q_link_owner", 4ull * d_.q_max);
-      L.q_link_ch = (u32*)dev("q_link_ch", 4ull * d_.q_max);
-      L.q_link_epoch = (u32*)dev("q_link_epoch", 4ull * d_.q_max);
-      L.lk_cnt = (u32*)dev("lk_cnt", 4ull * WORLD_MAX);
+      d_.links = 1;
+      d_.lk_cap = (u32)get("link_acks", 2ull * d_.deliv_max);
+      d_.conn_link = (u32*)dev("conn_link", 4ull * d_.c_max);
+      d_.conn_link_tq = (u32*)dev("conn_link_tq", 4ull * d_.c_max);
+      d_.conn_link_epoch = (u32*)dev("conn_link_epoch", 4ull * d_.c_max);
+      d_.link_conns = (u32*)dev("link_conns", 4ull * 64);
+      d_.n_link_conns = (u32*)dev("n_link_conns", 4);
+      d_.link_nbase = (u32*)dev("link_nbase", 4ull * d_.c_max);
+      d_.link_bbase = (u32*)dev("link_bbase", 4ull * d_.c_max);
+      d_.link_dbase = (u32*)dev("link_dbase", 4ull * WORLD_MAX);
+      d_.q_link_owner = (u32*)dev("q_link_owner", 4ull * d_.q_max);
+      d_.q_link_ch = (u32*)dev("q_link_ch", 4ull * d_.q_max);
+      d_.q_link_epoch = (u32*)dev("q_link_epoch", 4ull * d_.q_max);
+      d_.lk_cnt = (u32*)dev("lk_cnt", 4ull * WORLD_MAX);
       fill("q_link_ch", 0xff);
-      for (int p = 0; p < 2; ++p) {
-        std::string sfx = std::to_string(p);
-        ls_desc_[p] = (u8*)dev(("ls_desc" + sfx).c_str(), 64ull * d_.deliv_max + 64);
-        ls_pay_[p] = (u8*)dev(("ls_pay" + sfx).c_str(), d_.egress_cap + 64);
-        lk_send_[p] = (u8*)dev(("lk_send" + sfx).c_str(), 16ull * d_.world * L.lk_cap + 64);
-        rack_[p] = (u8*)dev(("rack" + sfx).c_str(), 16ull * d_.world * L.lk_cap + 64);
+    }
+    if (d_.persist)
+      for (int k = 0; k < PSLOTS; ++k) {   // store-record slots, shared by the parities (rotating per step)
+        const std::string ks = std::to_string(k);
+        persist_h_[k] = (const u8*)mapped(&d_.ps_persist[k], "persist" + ks, d_.persist_bytes + 64);
+        consumed_h_[k] = (const ConsumedRec*)mapped(&d_.ps_crec[k], "consumed" + ks,
+                                                    sizeof(ConsumedRec) * (u64)d_.persist_max + 64);
       }
-      for (int p = 0; p < 2; ++p) {
-        DS& io = io_[p];
-        io.links = 1; io.lk_cap = L.lk_cap;
-        io.conn_link = L.conn_link; io.conn_link_tq = L.conn_link_tq; io.conn_link_epoch = L.conn_link_epoch;
-        io.link_conns = L.link_conns; io.n_link_conns = L.n_link_conns; io.link_nbase = L.link_nbase;
-        io.link_bbase = L.link_bbase; io.link_dbase = L.link_dbase; io.q_link_owner = L.q_link_owner;
-        io.q_link_ch = L.q_link_ch; io.q_link_epoch = L.q_link_epoch; io.lk_cnt = L.lk_cnt;
-        io.lsend_desc = (RDesc*)ls_desc_[p]; io.lsend_pay = ls_pay_[p]; io.lk_send = (AckRec*)lk_send_[p];
-        io.rack = (const AckRec*)rack_[p ^ 1];   // the acks of the exchange this parity imports
+    // per-parity step IO on top of the shared state: step t uses set t % npar_, so step t+1's
+    // H2D and step t-1's D2H overlap step t's kernels (the graph of each parity is captured once)
+    for (int p = 0; p < npar_; ++p) {
+      const std::string sfx = std::to_string(p);
+      StepSlot& sp = par_[p];
+      HostIO& io = sp.io;
+      static_cast<DS&>(io) = d_;
+      if (p == 1)
+        for (auto& f : par1_) f(io);
+      io.in = (StepIn*)dev(("in" + sfx).c_str(), sizeof(StepIn));
+      io.segs = (const SegIn*)dev(("segs" + sfx).c_str(), sizeof(SegIn) * d_.seg_max);
+      // ingress payloads rotate over INGRESS_SLOTS buffers by step (StepIn.ingress): the
+      // next step's payload goes into a slot whose last reader (three steps back) is known
+      // done, so an early H2D never waits on the GPU
+      io.ingress = ing_[p].buf;
+      // outputs: device buffers the kernels fill, host-mapped ones the host reads (their host
+      // addresses resolved here, once: nothing on the step path looks a name up)
+      io.seg_out = (SegOut*)dev(("seg_out_d" + sfx).c_str(), sizeof(SegOut) * d_.seg_max);
+      io.seg_out_hh = (const SegOut*)mapped(&io.seg_out_h, "seg_out" + sfx, sizeof(SegOut) * d_.seg_max);
+      io.ctr_host_h = (const Counters*)mapped(&io.ctr_host, "ctr_host" + sfx, sizeof(Counters));
+      io.conn_out = (ConnOut*)dev(("conn_out_d" + sfx).c_str(), sizeof(ConnOut) * d_.c_max);
+      io.conn_out_hh = (const ConnOut*)mapped(&io.conn_out_h, "conn_out" + sfx, sizeof(ConnOut) * d_.c_max);
+      io.ctrl = (u8*)dev(("ctrl_d" + sfx).c_str(), d_.ctrl_cap);
+      io.ctrl_hh = (const u8*)mapped(&io.ctrl_h, "ctrl" + sfx, d_.ctrl_cap);
+      io.ctrl_rec = (CtrlRec*)dev(("ctrl_rec_d" + sfx).c_str(), sizeof(CtrlRec) * d_.seg_max * 2);
+      io.ctrl_rec_hh = (const CtrlRec*)mapped(&io.ctrl_rec_h, "ctrl_rec" + sfx, sizeof(CtrlRec) * d_.seg_max * 2);
+      io.grow_hh = (const RingMove*)mapped(&io.grow_h, "grow" + sfx, sizeof(RingMove) * GROW_MAX);
+      io.conn_conf_hh = (const u32*)mapped(&io.conn_conf_h, "conn_conf" + sfx, 4ull * d_.c_max);
+      io.xchg_h = (u32*)mapped(&io.xchg, "xchg" + sfx, 4ull * XC_WORDS);
+      // the step's descriptors stay in host-mapped memory: k_stage reads them over PCIe
+      // and writes the device copies (io.in / io.segs) the later kernels read.  Two H2D
+      // copies per step were runtime blit kernels on a third hardware queue, ordered behind
+      // the prefetched payload: ~50 us between the payload's arrival and the ingest
+      sp.stage_in = (StepIn*)mapped(&io.in_h, "stage_in" + sfx, sizeof(StepIn));
+      sp.stage_segs = (SegIn*)mapped(&io.segs_h, "stage_segs" + sfx, sizeof(SegIn) * d_.seg_max + 64);
+      // deferred control writes ridden by this parity's steps (pack_deltas)
+      sp.dl_h = (u8*)mapped(&io.delta_h, "delta" + sfx, DELTA_CAP);
+      // Basic.Get on the step: the requests (H2D with the step) and their answers
+      io.get_req = (const GetReq*)dev(("get_req" + sfx).c_str(), sizeof(GetReq) * GET_STEP_MAX);
+      io.get_out_hh = (GetOut*)mapped(&io.get_out_h, "get_out" + sfx, sizeof(GetOut) * GET_STEP_MAX);
+      sp.stage_gets = (GetReq*)pinned(("stage_gets" + sfx).c_str(), sizeof(GetReq) * GET_STEP_MAX);
+      io.unpause_req = (const u32*)dev(("unpause_req" + sfx).c_str(), 4ull * UNPAUSE_STEP_MAX);
+      sp.stage_unp = (u32*)pinned(("stage_unp" + sfx).c_str(), 4ull * UNPAUSE_STEP_MAX);
+      if (native_x_) {
+        sp.xs_desc = (u8*)dev(("xs_desc" + sfx).c_str(), 64ull * d_.xfer_desc_max + 64);
+        sp.xs_pay = (u8*)dev(("xs_pay" + sfx).c_str(), d_.xfer_bytes + 64);
+        sp.xr_desc = (u8*)dev(("xr_desc" + sfx).c_str(), 64ull * d_.import_max + 64);
+        sp.xr_pay = (u8*)dev(("xr_pay" + sfx).c_str(), d_.import_bytes + 64);
+      }
+      if (links_) {
+        sp.ls_desc = (u8*)dev(("ls_desc" + sfx).c_str(), 64ull * d_.deliv_max + 64);
+        sp.ls_pay = (u8*)dev(("ls_pay" + sfx).c_str(), d_.egress_cap + 64);
+        sp.lk_send = (u8*)dev(("lk_send" + sfx).c_str(), 16ull * d_.world * d_.lk_cap + 64);
+        sp.rack = (u8*)dev(("rack" + sfx).c_str(), 16ull * d_.world * d_.lk_cap + 64);
       }
     }
-    for (int p = 0; p < 2; ++p) io_[p].import_bytes = d_.import_bytes;
+    for (int p = 0; p < npar_; ++p) {   // (sharded engines have two parities) p packs into S[p], imports R[p^1]
+      StepSlot& sp = par_[p];
+      const StepSlot& other = par_[p ^ 1];
+      if (native_x_) {
+        sp.io.send_desc = (RDesc*)sp.xs_desc; sp.io.send_pay = sp.xs_pay;
+        sp.io.recv_desc = (const RDesc*)other.xr_desc; sp.io.recv_pay = other.xr_pay;
+      }
+      if (links_) {
+        sp.io.lsend_desc = (RDesc*)sp.ls_desc; sp.io.lsend_pay = sp.ls_pay; sp.io.lk_send = (AckRec*)sp.lk_send;
+        sp.io.rack = (const AckRec*)other.rack;   // the acks of the exchange this parity imports
+      }
+    }
     if (copy_mode_ == 3) init_sdma();
     HIPCHECK(hipStreamCreateWithFlags(&s_comp_, hipStreamNonBlocking));
     HIPCHECK(hipStreamCreateWithFlags(&s_h2d_, hipStreamNonBlocking));
@@ -643,8 +702,8 @@ class Engine {
     h2d_hsa_ = copy_mode_ == 3 && !sdma_ && d_.world == 1 && get("overlap", 1) == 0 && get("h2d_hsa", 0) != 0;
     if (h2d_hsa_)
       for (int k = 0; k < INGRESS_SLOTS; ++k)
-        if (hsa_signal_create(0, 0, nullptr, &ing_sig_[k]) != HSA_STATUS_SUCCESS ||
-            hsa_signal_create(0, 0, nullptr, &ing_sig2_[k]) != HSA_STATUS_SUCCESS)
+        if (hsa_signal_create(0, 0, nullptr, &ing_[k].sig) != HSA_STATUS_SUCCESS ||
+            hsa_signal_create(0, 0, nullptr, &ing_[k].sig2) != HSA_STATUS_SUCCESS)
           throw std::runtime_error("hsa_signal_create failed");
     // ingress payloads share the H2D stream: a stream of their own stalled the host for ~6 ms
     // in an early prefetch on some boxes (12+ MB copies; profiles/r4_summary.md)
@@ -657,12 +716,12 @@ class Engine {
       HIPCHECK(hipStreamCreateWithPriority(&s_ing_, hipStreamNonBlocking, hi));
     }
     for (int p = 0; p < npar_; ++p) {
-      HIPCHECK(hipEventCreateWithFlags(&ev_ing_[p], hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_pre_[p], hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_rest_[p], hipEventDisableTiming));
+      StepSlot& sp = par_[p];
+      for (hipEvent_t* ev : {&sp.ev_ing, &sp.ev_pre, &sp.ev_rest, &sp.ev_h2d, &sp.ev_done, &sp.ev_a, &sp.ev_ext})
+        HIPCHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
     }
-    for (int k = 0; k < INGRESS_SLOTS; ++k)
-      HIPCHECK(hipEventCreateWithFlags(&ev_ing_slot_[k], hipEventDisableTiming));
+    for (IngressSlot& ig : ing_) HIPCHECK(hipEventCreateWithFlags(&ig.ev_read, hipEventDisableTiming));
+    for (EgressSlot& es : eg_) HIPCHECK(hipEventCreateWithFlags(&es.ev_d2h, hipEventDisableTiming));
     // overlap (world 1): the step's ingest half runs on its own stream, next to the
     // previous step's routing / delivery half
     overlap_ = d_.world == 1 && get("overlap", 1) != 0;
@@ -678,13 +737,6 @@ class Engine {
     // after it saw the step finish (egress_copy)
     // (sharded ranks too: the step's last kernel -- phase B's -- opens the gate the same way)
     gated_ = copy_mode_ == 3 && get("egress_gate", 1) != 0;
-    for (int p = 0; p < npar_; ++p) {
-      HIPCHECK(hipEventCreateWithFlags(&ev_h2d_[p], hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_done_[p], hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_a_[p], hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&ev_ext_[p], hipEventDisableTiming));
-    }
-    for (int e = 0; e < EGRESS_SLOTS; ++e) HIPCHECK(hipEventCreateWithFlags(&ev_d2h_[e], hipEventDisableTiming));
     // ---- initial state
     fill("conn_dfirst", 0xff);
     fill("conn_ret_min", 0xff);
@@ -705,34 +757,36 @@ class Engine {
     // (a step that faulted before its last kernel), then let the copies finish
     if (copy_mode_ == 3)
       for (int e = 0; e < EGRESS_SLOTS; ++e) {
-        if (gate_sig_[e].handle) hsa_signal_store_screlease(gate_sig_[e], 0);
-        if (sdma_pending_[e] || tail_pending_[e]) {
+        EgressSlot& es = eg_[e];
+        if (es.gate_sig.handle) hsa_signal_store_screlease(es.gate_sig, 0);
+        if (es.sdma_pending || es.tail_pending) {
           try { sdma_wait(e); } catch (const std::exception&) {}   // (reported already)
         }
       }
-    for (int k = 0; k < INGRESS_SLOTS; ++k)
-      if (ing_sig_[k].handle) {
-        if (ing_hsa_[k]) (void)hsa_signal_wait_scacquire(ing_sig_[k], HSA_SIGNAL_CONDITION_EQ, 0, 2000 * block_ticks_,
-                                                          HSA_WAIT_STATE_BLOCKED);
-        if (ing_split_[k]) (void)hsa_signal_wait_scacquire(ing_sig2_[k], HSA_SIGNAL_CONDITION_EQ, 0, 2000 * block_ticks_,
-                                                            HSA_WAIT_STATE_BLOCKED);
+    for (IngressSlot& ig : ing_)
+      if (ig.sig.handle) {
+        if (ig.hsa) (void)hsa_signal_wait_scacquire(ig.sig, HSA_SIGNAL_CONDITION_EQ, 0, 2000 * block_ticks_,
+                                                    HSA_WAIT_STATE_BLOCKED);
+        if (ig.split) (void)hsa_signal_wait_scacquire(ig.sig2, HSA_SIGNAL_CONDITION_EQ, 0, 2000 * block_ticks_,
+                                                      HSA_WAIT_STATE_BLOCKED);
       }
     (void)hipStreamSynchronize(s_comp_);
     (void)hipStreamSynchronize(s_h2d_);
     if (s_h2d_alt_) (void)hipStreamSynchronize(s_h2d_alt_);
     (void)hipStreamSynchronize(s_pre_);
-    for (int k = 0; k < INGRESS_SLOTS; ++k)
-      if (ing_sig_[k].handle) { hsa_signal_destroy(ing_sig_[k]); hsa_signal_destroy(ing_sig2_[k]); }
+    for (IngressSlot& ig : ing_)
+      if (ig.sig.handle) { hsa_signal_destroy(ig.sig); hsa_signal_destroy(ig.sig2); }
     (void)hipStreamSynchronize(s_d2h_);
     for (int p = 0; p < npar_; ++p) {
-      if (graph_exec_[p]) (void)hipGraphExecDestroy(graph_exec_[p]);
-      if (graph_b_[p]) (void)hipGraphExecDestroy(graph_b_[p]);
-      (void)hipEventDestroy(ev_a_[p]);
-      (void)hipEventDestroy(ev_ext_[p]);
-      (void)hipEventDestroy(ev_h2d_[p]);
-      (void)hipEventDestroy(ev_done_[p]);
+      StepSlot& sp = par_[p];
+      if (sp.graph_exec) (void)hipGraphExecDestroy(sp.graph_exec);
+      if (sp.graph_b) (void)hipGraphExecDestroy(sp.graph_b);
+      (void)hipEventDestroy(sp.ev_a);
+      (void)hipEventDestroy(sp.ev_ext);
+      (void)hipEventDestroy(sp.ev_h2d);
+      (void)hipEventDestroy(sp.ev_done);
     }
-    for (int e = 0; e < EGRESS_SLOTS; ++e) (void)hipEventDestroy(ev_d2h_[e]);
+    for (EgressSlot& es : eg_) (void)hipEventDestroy(es.ev_d2h);
     if (ev_side_) (void)hipEventDestroy(ev_side_);
     if (s_x_) (void)hipStreamDestroy(s_x_);
     if (s_io_) (void)hipStreamDestroy(s_io_);
@@ -779,6 +833,13 @@ class Engine {
       return dp;
     }
     return b.ptr;
+  }
+
+  // a host-mapped buffer: its device address into *dptr, its host address back
+  template <class D>
+  void* mapped(D** dptr, const std::string& name, size_t bytes) {
+    *dptr = (D*)alloc(name.c_str(), bytes, true);
+    return bufs_[name].ptr;
   }
 
   // a named device range inside an allocation made with alloc()
@@ -864,11 +925,11 @@ class Engine {
     o["egress_ref_min"] = ref_min_;
     o["egress_slots"] = EGRESS_SLOTS;
     o["parities"] = npar_;
-    { u32 e = 0; while (copy_mode_ == 3 && e < 32 && !(((u32)sdma_engine_ >> e) & 1u)) ++e; o["sdma_engine"] = copy_mode_ == 3 ? (int)e : -1; }
-    { u32 e = 0; while (sdma_engine2_ && e < 32 && !(((u32)sdma_engine2_ >> e) & 1u)) ++e; o["sdma_engine2"] = sdma_engine2_ ? (int)e : -1; }
-    { u32 e = 0; while (h2d_hsa_ && e < 32 && !(((u32)ing_engine_ >> e) & 1u)) ++e; o["h2d_hsa_engine"] = h2d_hsa_ ? (int)e : -1; }
-    { u32 e = 0; while (h2d_hsa_ && ing_engine2_ && e < 32 && !(((u32)ing_engine2_ >> e) & 1u)) ++e;
-      o["h2d_hsa_engine2"] = h2d_hsa_ && ing_engine2_ ? (int)e : -1; }
+    auto engine_no = [](bool used, u32 mask) { return used && mask ? __builtin_ctz(mask) : -1; };   // (one-bit masks)
+    o["sdma_engine"] = engine_no(copy_mode_ == 3, (u32)sdma_engine_);
+    o["sdma_engine2"] = engine_no(true, (u32)sdma_engine2_);
+    o["h2d_hsa_engine"] = engine_no(h2d_hsa_, (u32)ing_engine_);
+    o["h2d_hsa_engine2"] = engine_no(h2d_hsa_, (u32)ing_engine2_);
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
     o["restore_max"] = restore_max_;
     o["xfer_desc_max"] = d_.xfer_desc_max; o["xfer_bytes"] = d_.xfer_bytes; o["world_max"] = WORLD_MAX;
@@ -882,6 +943,135 @@ class Engine {
     return o;
   }
 
+ private:
+  // ---- configuration (fixed by the constructor)
+  int device_ = 0;
+  u32 n_cu_ = 256;   // compute units of the device (grid caps of the block-per-segment / group kernels)
+  DS d_;
+  bool graph_enabled_ = true;
+  bool overlap_ = false;   // world 1: the ingest half on its own stream next to the previous routing half
+  int npar_ = 2;           // per-step IO sets in use (of NPAR_MAX)
+  bool lag_ = false, native_x_ = false, links_ = false;
+  u32 restore_max_ = 0;
+  u64 carry_budget_ = 0;
+  int copy_mode_ = 0;      // cfg copy_engine
+  bool sdma_ = true;       // copy_engine 1: NoCU copy requests
+  u32 copy_wgs_ = 16;
+  int sdma_pref_ = -1, sdma_split_ = 1;
+  bool gated_ = false;     // egress D2H queued at launch behind a gate (HSA SDMA)
+  bool h2d_hsa_ = false;   // ingress payloads in GPU-mapped host memory go to an SDMA engine through HSA
+  bool h2d_split_cfg_ = false;
+  u64 h2d_split_min_ = 4u << 20;
+  u32 wait_ms_ = 10000;    // bounded_wait deadline
+  int ref_back_ = -1;      // egress by reference: steps back a body may be referenced (-1 off)
+  u32 ref_min_ = 256;      // smallest referenced body (smaller ones are cheaper inline)
+ public:
+  u32 dcap_bytes_ = 0;     // StepIn.dcap_bytes of the next submitted steps (deliver_cap_bytes)
+ private:
+  // ---- buffers
+  std::map<std::string, Buf> bufs_;
+  u64 total_bytes_ = 0;
+  u64 egress_alloc_ = 0;
+  u32 ntiles_max_ = 0;
+  u64* scan_status_ = nullptr;
+  u32* scan_ctl_ = nullptr;
+  u64* scan_status_ing_ = nullptr;   // the ingest half's own look-back state
+  u32* scan_ctl_ing_ = nullptr;
+  u32 scan_smax_ = 0;
+  u8* work_p1_ = nullptr;
+  // parity 1's copies of the per-step buffers (parity 0 keeps d_'s)
+  std::vector<std::function<void(DS&)>> par1_;
+  template <class T>
+  void dup(T* DS::*m, const char* name, size_t bytes) {
+    T* p1 = (T*)alloc((std::string(name) + "_p1").c_str(), bytes, false);
+    par1_.push_back([m, p1](DS& io) { io.*m = p1; });
+  }
+  u64 get_cap_ = 0;                  // Basic.Get between steps
+  u8 *get_out_dev_ = nullptr, *get_out_h_ = nullptr;
+  GetRes *get_res_dev_ = nullptr, *get_res_h_ = nullptr;
+  const u8* persist_h_[PSLOTS] = {};            // store-record slots (persist)
+  const ConsumedRec* consumed_h_[PSLOTS] = {};
+  u32* wblock_h_ = nullptr;
+  // ---- slots
+  StepSlot par_[NPAR_MAX];
+  EgressSlot eg_[EGRESS_SLOTS];
+  IngressSlot ing_[INGRESS_SLOTS];
+  StepSlot& par(int p) {
+    if (p < 0 || p >= npar_) throw std::runtime_error("no such parity: " + std::to_string(p));
+    return par_[p];
+  }
+  bool any_inflight() const {
+    for (int p = 0; p < npar_; ++p)
+      if (par_[p].inflight) return true;
+    return false;
+  }
+  // ---- step path
+  u64 seq_ = 0;
+  hipStream_t s_comp_ = nullptr, s_h2d_ = nullptr, s_d2h_ = nullptr, s_ing_ = nullptr;
+  hipStream_t s_pre_ = nullptr;       // payloads (= s_h2d_)
+  hipStream_t s_h2d_alt_ = nullptr;   // odd steps' H2D (cfg h2d_alt)
+  hipStream_t h2d_of(u64 step) const { return (s_h2d_alt_ && (step & 1)) ? s_h2d_alt_ : s_h2d_; }
+  std::vector<GetReq> pend_gets_;     // Basic.Get requests for the next submit
+  DeltaStage dl_;                     // deferred control writes for the next submit
+  u32 spill_req_[3] = {0, 0, 0};      // stage_spill for the next submitted step (dl_.mu)
+  bool h2d_fault_ = false, gate_fault_ = false, wait_failed_ = false;
+  void* h2d_dummy_ = nullptr;         // pinned host word of inject_h2d_fault
+  void* gate_dummy_ = nullptr;        // device word a faulted step's gate store lands in
+  double ht_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // host_times() phases
+  // ---- HSA copies (copy_engine 3)
+  hsa_agent_t gpu_agent_{}, cpu_agent_{};
+  hsa_amd_sdma_engine_id_t sdma_engine_{}, sdma_engine2_{}, tail_engine_{};
+  hsa_amd_sdma_engine_id_t ing_engine_{}, ing_engine2_{};   // ingress; a split payload's second engine (0: no split)
+  u64 spin_ticks_ = 0, block_ticks_ = 0;   // bounded_wait: active spin / blocked slice (timestamp ticks)
+  u64 eg_hist_[4] = {0, 0, 0, 0};          // the last steps' egress bytes (spec_bytes)
+  u32 eg_hist_i_ = 0;
+  u64 eg_stats_[4] = {0, 0, 0, 0};
+  // ---- exchange
+  std::vector<u32> lag_recv_;
+  u64 lag_stream_ = 0;
+  bool xfer_set_ = false;
+  std::unique_ptr<cmqx::RcclXchg> rccl_;
+  std::unique_ptr<cmqx::ShmXchg> shm_;
+  std::unique_ptr<cmqx::ShmXchg> cshm_;   // rccl + host shared-memory count exchange
+  std::vector<int> xmembers_;
+  int xtimeout_ms_ = 10000;
+  bool xfailover_ = false;
+  bool x_wait_ = false;              // phase B waits on the RCCL bulk transfer
+  u64 xseq_ = 0;
+  // asynchronous exchange (xchg_setup async=true): one job at a time on the exchange thread
+  bool async_x_ = false;
+  std::thread xth_;
+  std::mutex xmu_;
+  std::condition_variable xcv_;
+  bool xstop_ = false, xjob_ = false, xbusy_ = false, xres_ = false;
+  int xq_ = 0, xres_rc_ = 0;
+  u32 xflags_ = 0, xres_orf_ = 0, xjob_seq_ = 0, xseq_job_ = 0;
+  std::string xerr_;
+  u32* xflag_h_ = nullptr;           // host-mapped [0] last finished job, [1] a device wait gave up
+  u32* xflag_d_ = nullptr;
+  std::mutex cap_mu_;                // graph captures vs the exchange thread's HIP calls
+  hipStream_t s_x_ = nullptr;        // the shared-memory exchange's copies
+  // ---- side operations, table IO
+  static constexpr u32 COLD_BATCH = 1u << 16;   // cold records per pick / scan call
+  struct Side { int kind; u32 a; u64 b, c; u32 max_n; u64 max_bytes; u32 n; bool launched; };
+  Side side_{SIDE_NONE, 0, 0, 0, 0, 0, 0, false};
+  std::mutex side_mu_;
+  std::condition_variable side_cv_;
+  hipEvent_t ev_side_ = nullptr;
+  void* side_h_ = nullptr;      // host-mapped: [count @0][ColdRec[] @64]
+  void* side_d_ = nullptr;
+  i64* side_live_h_ = nullptr;
+  ColdRec* cold_recs_ = nullptr;
+  u32* cold_cnt_ = nullptr;
+  unsigned long long* cold_bytes_ = nullptr;
+  unsigned long long* spill_moved_ = nullptr;
+  u64* cold_end_ = nullptr;
+  std::mutex io_mu_;
+  hipStream_t s_io_ = nullptr;       // upload / download
+  // ---- C API
+  CmqEngineApi api_{};
+  std::string err_;
+ public:
   // ------------------------------------------------------------- step (pipelined)
   // submit(): stage step t's ingress on the H2D stream and launch parity t&1's graph on
   // the compute stream behind it.  wait_results(p) -> host-mapped SegOut/Counters/ConnOut
@@ -908,28 +1098,30 @@ class Engine {
     const u64 step = seq_;
     if (nseg > d_.seg_max) throw std::runtime_error("too many segments");
     if (payload_len > d_.ingress_cap) throw std::runtime_error("ingress payload exceeds ingress_cap");
-    int p = (int)(seq_ % (u64)npar_);
-    if (inflight_[p]) throw std::runtime_error("submit: results of the previous step of this parity not collected");
-    HIPCHECK(hipEventSynchronize(ev_h2d_[p]));  // staging buffers of step t-2 are free
+    const int p = (int)(seq_ % (u64)npar_);
+    StepSlot& sp = par_[p];
+    if (sp.inflight) throw std::runtime_error("submit: results of the previous step of this parity not collected");
+    HIPCHECK(hipEventSynchronize(sp.ev_h2d));  // staging buffers of step t-2 are free
     // the payload first: the H2D is the step's longest stage and nothing below changes what
     // it copies (the slot's last reader, step t - INGRESS_SLOTS, is finished: its results were
     // collected before step t-2's).  It may already be on its way (prefetch): then only the
     // step's descriptors follow it on the H2D stream
     const int is = (int)(seq_ % INGRESS_SLOTS);
-    const bool pre = pre_[p];
-    if (pre && (pre_seq_[p] != step || pre_ptr_[p] != payload_ptr || pre_len_[p] != payload_len))
+    IngressSlot& ig = ing_[is];
+    const bool pre = sp.pre;
+    if (pre && (sp.pre_seq != step || sp.pre_ptr != payload_ptr || sp.pre_len != payload_len))
       throw std::runtime_error("submit: payload differs from the one prefetched for this step");
-    pre_[p] = false;
+    sp.pre = false;
     {   // overlapped engines move payloads on their own stream (prefetches run ahead of the
         // small per-step copies there; the ingest half waits for both)
       hipStream_t ps = overlap_ ? s_pre_ : h2d_of(step);
       if (payload_len && !pre) ingress_copy(step, is, payload_ptr, payload_len, ps);
-      else if (!payload_len) ing_hsa_[is] = false;
+      else if (!payload_len) ig.hsa = false;
     }
-    StepIn* in = stage_in_[p];
+    StepIn* in = sp.stage_in;
     *in = StepIn{};
-    in->h2d_sig = ing_hsa_[is] ? (u64)&((amd_signal_t*)ing_sig_[is].handle)->value : 0;
-    in->h2d_sig2 = ing_hsa_[is] && ing_split_[is] ? (u64)&((amd_signal_t*)ing_sig2_[is].handle)->value : 0;
+    in->h2d_sig = ig.hsa ? (u64)&((amd_signal_t*)ig.sig.handle)->value : 0;
+    in->h2d_sig2 = ig.hsa && ig.split ? (u64)&((amd_signal_t*)ig.sig2.handle)->value : 0;
     if (in->h2d_sig && h2d_fault_) {   // (tests) the step waits on a word no copy completes
       h2d_fault_ = false;
       *(volatile i64*)h2d_dummy_ = 1;
@@ -937,10 +1129,10 @@ class Engine {
       in->h2d_sig2 = 0;
       in->h2d_polls = 4096;
     }
-    h2d_addr_[p] = in->h2d_sig;
-    h2d_addr2_[p] = in->h2d_sig2;
+    sp.h2d_addr = in->h2d_sig;
+    sp.h2d_addr2 = in->h2d_sig2;
     // the step's stream waits for the H2D stream only when a runtime copy of this step is on it
-    h2d_hip_[p] = !h2d_hsa_ || (payload_len && !ing_hsa_[is]) || !pend_gets_.empty();
+    sp.h2d_hip = !h2d_hsa_ || (payload_len && !ig.hsa) || !pend_gets_.empty();
     in->nseg = nseg;
     in->ref_back = ref_back_ >= 0 ? (u32)ref_back_ : ref_back_ == -2 ? REF_SPILL_ONLY : 0xffffffffu;
     in->ref_min = ref_min_;
@@ -952,40 +1144,40 @@ class Engine {
     in->id_ms = id_ms;
     in->worker = worker;
     const int e = (int)(seq_ % EGRESS_SLOTS);
-    in->egress = (u64)egress_dev_[e];
+    EgressSlot& es = eg_[e];
+    in->egress = (u64)es.dev;
     // the slot's previous D2H (step t - EGRESS_SLOTS, long finished) must be complete before
     // its gate is re-armed and its buffer rendered into again
-    if (copy_mode_ == 3 && (sdma_pending_[e] || tail_pending_[e])) { HostTimer t(&ht_[1]); sdma_wait(e); }
-    spec_[e] = gated_ ? spec_bytes() : 0;
+    if (copy_mode_ == 3 && (es.sdma_pending || es.tail_pending)) { HostTimer t(&ht_[1]); sdma_wait(e); }
+    es.spec = gated_ ? spec_bytes() : 0;
     in->gate = 0;
-    if (spec_[e]) {
-      hsa_signal_store_screlease(gate_sig_[e], 1);
-      in->gate = (u64)&((amd_signal_t*)gate_sig_[e].handle)->value;
+    if (es.spec) {
+      hsa_signal_store_screlease(es.gate_sig, 1);
+      in->gate = (u64)&((amd_signal_t*)es.gate_sig.handle)->value;
       if (gate_fault_) {   // (tests) the last kernel opens a scratch word instead: the copy never starts
         gate_fault_ = false;
         in->gate = (u64)gate_dummy_;
       }
     }
-    in->ingress = (u64)ingress_slot_[is];
+    in->ingress = (u64)ig.buf;
     in->pslot = (u32)(seq_ % PSLOTS);
-    pslot_of_[p] = (int)in->pslot;
-    slot_of_[p] = e;
-    launch_seq_[p] = step;
-    if (sb) memcpy(stage_segs_[p], segp, sb);
+    sp.pslot = (int)in->pslot;
+    sp.slot = e;
+    sp.launch_seq = step;
+    if (sb) memcpy(sp.stage_segs, segp, sb);
     // staged Basic.Get requests ride this step; their answers start out RETRY (a queue the
     // device cannot serve now leaves it so)
     in->nget = (u32)pend_gets_.size();
     if (in->nget) {
-      memcpy(stage_gets_[p], pend_gets_.data(), sizeof(GetReq) * in->nget);
-      GetOut* go = (GetOut*)buf("get_out" + std::to_string(p)).ptr;
-      for (u32 i = 0; i < in->nget; ++i) go[i] = GetOut{GS_RETRY, 0};
-      HIPCHECK(hipMemcpyAsync((void*)io_[p].get_req, stage_gets_[p], sizeof(GetReq) * in->nget,
+      memcpy(sp.stage_gets, pend_gets_.data(), sizeof(GetReq) * in->nget);
+      for (u32 i = 0; i < in->nget; ++i) sp.io.get_out_hh[i] = GetOut{GS_RETRY, 0};
+      HIPCHECK(hipMemcpyAsync((void*)sp.io.get_req, sp.stage_gets, sizeof(GetReq) * in->nget,
                               hipMemcpyHostToDevice, h2d_of(step)));
       pend_gets_.clear();
     }
-    nget_[p] = in->nget;
+    sp.nget = in->nget;
     {   // body tiering asked for by the control plane rides this step (k_dequeue)
-      std::lock_guard<std::mutex> g(dl_mu_);
+      std::lock_guard<std::mutex> g(dl_.mu);
       in->spill_frac = spill_req_[0];
       in->spill_hot = spill_req_[1];
       in->spill_budget = spill_req_[2];
@@ -994,18 +1186,18 @@ class Engine {
     // unpaused with them: a connection resumed in this step finds every write staged
     // before its unpause applied (k_stage applies the writes first)
     u32 nunp = 0;
-    in->delta_bytes = pack_deltas(p, stage_unp_[p], &nunp);
+    in->delta_bytes = dl_.pack_deltas(sp.dl_h, sp.stage_unp, &nunp);
     in->nunp = nunp;
-    nunp_[p] = nunp;
+    sp.nunp = nunp;
     if (in->nunp)
-      HIPCHECK(hipMemcpyAsync((void*)io_[p].unpause_req, stage_unp_[p], 4ull * in->nunp, hipMemcpyHostToDevice,
+      HIPCHECK(hipMemcpyAsync((void*)sp.io.unpause_req, sp.stage_unp, 4ull * in->nunp, hipMemcpyHostToDevice,
                               h2d_of(step)));
-    dl_step_[p] = in->delta_bytes;
-    if (in->nunp) h2d_hip_[p] = true;
-    if (overlap_) HIPCHECK(hipEventRecord(ev_pre_[p], s_pre_));
-    HIPCHECK(hipEventRecord(ev_h2d_[p], overlap_ ? s_h2d_ : h2d_of(step)));
-    inflight_[p] = true;
-    staged_[p] = true;
+    sp.dl_step = in->delta_bytes;
+    if (in->nunp) sp.h2d_hip = true;
+    if (overlap_) HIPCHECK(hipEventRecord(sp.ev_pre, s_pre_));
+    HIPCHECK(hipEventRecord(sp.ev_h2d, overlap_ ? s_h2d_ : h2d_of(step)));
+    sp.inflight = true;
+    sp.staged = true;
     ++seq_;
     if (!defer) launch(p);
     return p;
@@ -1022,13 +1214,12 @@ class Engine {
     if (d_.world != 1 || !payload_len) return false;   // (s_pre_ is s_h2d_: the step waits for it)
     Range rg("chanamq.step.prefetch");
     u64 tgt = seq_;
-    int p = (int)(tgt % (u64)npar_);
-    if (pre_[p]) {   // the next submit's payload is queued already: the one after it
+    if (par_[tgt % (u64)npar_].pre) {   // the next submit's payload is queued already: the one after it
       tgt = seq_ + 1;
-      p = (int)(tgt % (u64)npar_);
-      if (pre_[p]) return false;
+      if (par_[tgt % (u64)npar_].pre) return false;
     }
-    if (staged_[p]) throw std::runtime_error("prefetch: this step's payload is already queued");
+    StepSlot& sp = par_[tgt % (u64)npar_];
+    if (sp.staged) throw std::runtime_error("prefetch: this step's payload is already queued");
     if (payload_len > d_.ingress_cap) throw std::runtime_error("ingress payload exceeds ingress_cap");
     // the slot's last reader: the ingest of step tgt - INGRESS_SLOTS, collected by now in
     // the drivers' order (bench / front end prefetch t+1 once t-2 is finished); if not,
@@ -1036,271 +1227,61 @@ class Engine {
     const int is = (int)(tgt % INGRESS_SLOTS);
     hipStream_t ps = overlap_ ? s_pre_ : h2d_of(tgt);
     ingress_copy(tgt, is, payload_ptr, payload_len, ps);
-    pre_[p] = true;
-    pre_seq_[p] = tgt;
-    pre_ptr_[p] = payload_ptr;
-    pre_len_[p] = payload_len;
+    sp.pre = true;
+    sp.pre_seq = tgt;
+    sp.pre_ptr = payload_ptr;
+    sp.pre_len = payload_len;
     return true;
   }
 
-  // ---- deferred control writes (no pipeline drain): the control plane stages table writes
-  // while steps run; the next submitted step carries them (k_stage applies them first).
-  // Any thread.  Writes to the same bytes: the last one wins (records never overlap).
-  void stage_write(u64 dst, const u8* data, u64 n) {
-    if (!n) return;
-    // one record must fit a step's delta buffer with its header (a larger one
-    // was never packed and kept the stepper spinning on host_work)
-    if (n + 64 > DELTA_CAP) throw std::runtime_error("stage_write: a write larger than one step's delta buffer");
-    std::lock_guard<std::mutex> g(dl_mu_);
-    if (dl_.empty()) new_batch();
-    DlBatch& bt = dl_.back();
-    const u64 a = dst, e = dst + n;
-    auto it = bt.w.lower_bound(a);
-    if (it != bt.w.begin()) --it;
-    std::vector<std::pair<u64, std::string>> keep;
-    while (it != bt.w.end() && it->first < e) {
-      const u64 s0 = it->first, s1 = s0 + it->second.size();
-      if (s1 <= a) { ++it; continue; }
-      if (s0 < a) keep.emplace_back(s0, it->second.substr(0, a - s0));
-      if (s1 > e) keep.emplace_back(e, it->second.substr(e - s0));
-      bt.bytes -= it->second.size();
-      dl_bytes_ -= it->second.size();
-      it = bt.w.erase(it);
+  // the agent address of a payload in page-locked host memory (hipHostMalloc /
+  // hipHostRegister), 0 for pageable memory (the runtime's copy stages that)
+  static u64 ingress_src(u64 ptr) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, (const void*)ptr) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
     }
-    for (auto& kv : keep) {
-      bt.bytes += kv.second.size();
-      dl_bytes_ += kv.second.size();
-      bt.w.emplace(kv.first, std::move(kv.second));
-    }
-    bt.w.emplace(a, std::string((const char*)data, n));
-    bt.bytes += n;
-    dl_bytes_ += n;
-  }
-  void stage_write_buf(const std::string& name, py::buffer data, size_t offset) {
-    py::buffer_info info = data.request();
-    const size_t n = (size_t)info.size * info.itemsize;
-    const Buf& b = buf(name);
-    if (offset + n > b.bytes) throw std::runtime_error("stage_write overflows " + name);
-    if (b.host) { memcpy((u8*)b.ptr + offset, info.ptr, n); return; }   // host-mapped: direct
-    stage_write((u64)b.ptr + offset, (const u8*)info.ptr, n);
-  }
-  void stage_mark_dirty(u32 ch) {
-    if (ch >= d_.c_max * d_.chpc) throw std::runtime_error("stage_mark_dirty: bad channel slot");
-    std::lock_guard<std::mutex> g(dl_mu_);
-    if (dl_.empty()) new_batch();
-    auto& dv = dl_.back().dirty;
-    for (u32 c : dv)
-      if (c == ch) return;
-    dv.push_back(ch);
-  }
-  // a light control section's staging: everything staged until stage_end() forms one batch
-  // that no step takes before the section closed it (a step packing in the middle of a
-  // section split a command's consumer rows and q_cons lists over two steps)
-  void stage_begin() {
-    std::lock_guard<std::mutex> g(dl_mu_);
-    ++dl_open_;
-    if (dl_.empty() || !dl_.back().open) new_batch();
-  }
-  void stage_end() {
-    std::lock_guard<std::mutex> g(dl_mu_);
-    if (dl_open_) --dl_open_;
-    if (!dl_open_)
-      for (auto& bt : dl_) bt.open = false;
-  }
-  void new_batch() {   // (dl_mu_ held)
-    dl_.emplace_back();
-    dl_.back().open = dl_open_ > 0;
-    dl_.back().id = dl_next_id_++;
-  }
-  // batch ids (light sections tie their replies to them, Frontend::send_after): 0 = the
-  // batch staging goes into now (the next one to be created when none is open), 1 = every
-  // batch up to this id was taken by a submitted step (or applied by flush_deltas)
-  u64 dl_state(int which) {
-    std::lock_guard<std::mutex> g(dl_mu_);
-    if (which == 2) return dl_open_;      // (diagnostics: open light sections, batches queued)
-    if (which == 3) return dl_.size();
-    if (which == 1) {   // (closed batches with nothing in them count as taken: no step needs to carry them)
-      for (auto& bt : dl_)
-        if (bt.open || !bt.w.empty() || !bt.dirty.empty() || !bt.unp.empty()) return bt.id - 1;
-      return dl_next_id_ - 1;
-    }
-    // outside a light section nothing is staged for the caller: no batch to wait for
-    return (!dl_.empty() && dl_.back().open) ? dl_.back().id : 0;
-  }
-  // from the next submitted step on, every step moves queued bodies in the oldest frac/65536
-  // of the HBM log (past the first `hot` entries of a queue with consumers) to the host
-  // spill ring, at most `budget` bytes a step -- spill() without the pipeline drain; frac 0
-  // stops it.  Any thread.
-  void stage_spill(u32 frac, u32 hot, u32 budget) {
-    if (!d_.spill_bytes) return;
-    std::lock_guard<std::mutex> g(dl_mu_);
-    spill_req_[0] = frac; spill_req_[1] = hot; spill_req_[2] = budget;
-  }
-  // (records, data bytes, channels to mark) staged and not yet taken by a step
-  py::tuple deltas_pending() {
-    std::lock_guard<std::mutex> g(dl_mu_);
-    size_t nrec = 0, nd = 0;
-    for (auto& bt : dl_) { nrec += bt.w.size(); nd += bt.dirty.size(); }
-    return py::make_tuple(nrec, dl_bytes_, nd);
-  }
-  bool host_work() {
-    std::lock_guard<std::mutex> g(dl_mu_);
-    if (!unp_ready_.empty() || side_queued()) return true;
-    for (auto& bt : dl_) {
-      if (bt.open) break;   // (staged by a section still running: stage_end wakes the stepper)
-      if (!bt.w.empty() || !bt.dirty.empty() || !bt.unp.empty()) return true;
-    }
-    return false;
-  }
-  bool has_deltas() {
-    std::lock_guard<std::mutex> g(dl_mu_);
-    for (auto& bt : dl_)
-      if (!bt.w.empty() || !bt.dirty.empty()) return true;
-    return false;
-  }
-  // staged batches, oldest first, into parity p's host-mapped delta buffer: bytes used (0 =
-  // none).  The oldest batch may go in part (what does not fit -- records or bytes -- stays
-  // for a later step; records are independent bytes, and the control plane keeps a change
-  // set within one step by cutting its batches at deltas_pending() limits); later closed
-  // batches ride the same step whole, as long as they fit and write no byte an earlier
-  // record of the step writes (k_apply_deltas applies a step's records in parallel).  One
-  // batch per step capped the light sections at the step rate: under connection / RPC
-  // churn on a slower (durable) broker they queued up until a full pause flushed them.
-  // A batch's unpauses go with its last records to unp (at most UNPAUSE_STEP_MAX, *nunp) or,
-  // with unp null (flush_deltas: no step), to unp_ready_ for the next submitted step.
-  u32 pack_deltas(int p, u32* unp, u32* nunp) {
-    std::lock_guard<std::mutex> g(dl_mu_);
-    u32 nu = 0;
-    auto take_unp = [&](std::vector<u32>& v) {
-      size_t k = 0;
-      for (; k < v.size(); ++k) {
-        if (!unp) { unp_ready_.push_back(v[k]); continue; }
-        if (nu == UNPAUSE_STEP_MAX) break;
-        unp[nu++] = v[k];
-      }
-      v.erase(v.begin(), v.begin() + k);
-    };
-    auto done = [&](u32 r) { if (nunp) *nunp = nu; return r; };
-    if (unp) take_unp(unp_ready_);
-    // a step (unp set) never takes a batch a light section is still staging into;
-    // flush_deltas (between steps, the control plane holds the engine) takes everything
-    auto usable = [&](const DlBatch& bt) { return !(unp && bt.open); };
-    // leading batches with no writes: their unpauses only
-    while (!dl_.empty() && usable(dl_.front()) && dl_.front().w.empty() && dl_.front().dirty.empty()) {
-      take_unp(dl_.front().unp);
-      if (!dl_.front().unp.empty()) return done(0);   // (the step's unpause list is full)
-      if (dl_.size() == 1 && dl_.front().open) { dl_.pop_front(); break; }
-      dl_.pop_front();
-    }
-    if (dl_.empty() || !usable(dl_.front()) || (dl_.front().w.empty() && dl_.front().dirty.empty())) return done(0);
-    // ---- plan: how many records of the first batch, then which whole batches follow
-    u64 nrec = 0, nchunk = 0, ndirty = 0;
-    std::map<u64, u64> iv;   // byte ranges [dst, end) written by the records planned so far
-    auto overlaps = [&](u64 d0, u64 d1) {
-      auto it = iv.lower_bound(d0);
-      if (it != iv.end() && it->first < d1) return true;
-      if (it != iv.begin() && std::prev(it)->second > d0) return true;
-      return false;
-    };
-    auto need = [&](u64 r, u64 dn, u64 ch) { return 16 + 16 * r + ((4 * dn + 15) & ~15ull) + 16 * ch; };
-    DlBatch& b0 = dl_.front();
-    const u64 nd0 = std::min<u64>(b0.dirty.size(), 4096);
-    u64 n0 = 0;
-    for (auto& kv : b0.w) {
-      const u64 ch = (kv.second.size() + 15) / 16;
-      if (nrec == DELTA_REC_MAX || need(nrec + 1, nd0, nchunk + ch) > DELTA_CAP) break;
-      ++nrec;
-      nchunk += ch;
-      iv[kv.first] = kv.first + kv.second.size();
-      ++n0;
-    }
-    ndirty = nd0;
-    size_t nwhole = 0;   // later batches taken whole
-    if (n0 == b0.w.size() && nd0 == b0.dirty.size() && b0.unp.size() + nu <= UNPAUSE_STEP_MAX) {
-      u32 nu_plan = nu + (u32)b0.unp.size();
-      for (size_t k = 1; k < dl_.size(); ++k) {
-        DlBatch& bt = dl_[k];
-        if (!usable(bt)) break;
-        u64 r = nrec, ch = nchunk;
-        const u64 dn = ndirty + bt.dirty.size();
-        bool ok = dn <= 4096 && nu_plan + bt.unp.size() <= UNPAUSE_STEP_MAX;
-        for (auto it = bt.w.begin(); ok && it != bt.w.end(); ++it) {
-          ++r;
-          ch += (it->second.size() + 15) / 16;
-          ok = r <= DELTA_REC_MAX && need(r, dn, ch) <= DELTA_CAP &&
-               !overlaps(it->first, it->first + it->second.size());
-        }
-        if (!ok) break;
-        for (auto& kv : bt.w) iv[kv.first] = kv.first + kv.second.size();
-        nrec = r;
-        nchunk = ch;
-        ndirty = dn;
-        nu_plan += (u32)bt.unp.size();
-        ++nwhole;
-      }
-    }
-    // ---- write: head, records, dirty channels, data
-    u8* o = dl_h_[p];
-    DeltaHead* h = (DeltaHead*)o;
-    h->nrec = (u32)nrec; h->ndirty = (u32)ndirty; h->nchunk = (u32)nchunk; h->pad = 0;
-    DeltaRec* recs = (DeltaRec*)(o + sizeof(DeltaHead));
-    u32* dirty = (u32*)(recs + nrec);
-    u8* data = (u8*)dirty + ((4ull * ndirty + 15) & ~15ull);
-    u64 r = 0, c = 0, di = 0;
-    auto put = [&](DlBatch& bt, u64 nr, u64 ndr) {
-      u64 k = 0;
-      for (auto it = bt.w.begin(); it != bt.w.end() && k < nr; ++k) {
-        recs[r].dst = it->first;
-        recs[r].len = (u32)it->second.size();
-        recs[r].chunk0 = (u32)c;
-        memcpy(data + 16 * c, it->second.data(), it->second.size());
-        c += (it->second.size() + 15) / 16;
-        bt.bytes -= it->second.size();
-        dl_bytes_ -= it->second.size();
-        it = bt.w.erase(it);
-        ++r;
-      }
-      for (u64 k2 = 0; k2 < ndr; ++k2) dirty[di++] = bt.dirty[k2];
-      bt.dirty.erase(bt.dirty.begin(), bt.dirty.begin() + ndr);
-    };
-    put(b0, n0, nd0);
-    size_t gone = 0;   // leading batches fully taken (unpauses included)
-    for (size_t k = 0; k <= nwhole; ++k) {
-      DlBatch& bt = dl_[k];
-      if (k) put(bt, bt.w.size(), bt.dirty.size());
-      if (!bt.w.empty() || !bt.dirty.empty()) break;   // (the first batch went in part)
-      take_unp(bt.unp);   // the whole batch went: its unpauses ride along
-      if (!bt.unp.empty()) break;
-      ++gone;
-    }
-    for (size_t k = 0; k < gone; ++k) dl_.pop_front();
-    ++dl_steps_;
-    return done((u32)((data - o) + 16 * c));
-  }
-  // between steps (the control plane holds the engine): apply what is staged now
-  void flush_deltas() {
-    if (!has_deltas()) return;
-    if (inflight_[0] || inflight_[1]) throw std::runtime_error("flush_deltas() between steps only");
-    sync();
-    while (has_deltas()) {
-      if (!pack_deltas(0, nullptr, nullptr)) break;
-      hipLaunchKernelGGL(k_apply_deltas, dim3(1), dim3(1024), 0, s_comp_, io_[0], io_[0].delta_h);
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipStreamSynchronize(s_comp_));
-    }
+    return a.type == hipMemoryTypeHost && a.devicePointer ? (u64)a.devicePointer : 0;
   }
 
-  // a paused connection (its control command answered) resumes with the next submitted
-  // step: k_stage clears its flag before the frame scan reads it, so the host never writes
-  // device state while steps are in flight.  Any thread.
-  void stage_unpause(u32 conn) {
-    if (conn >= d_.c_max) throw std::runtime_error("stage_unpause: bad connection");
-    std::lock_guard<std::mutex> g(dl_mu_);
-    if (dl_.empty()) new_batch();
-    auto& v = dl_.back().unp;   // with the writes staged before it
-    for (u32 c : v)
-      if (c == conn) return;
-    v.push_back(conn);
+  // a step's payload into ingress slot is: on the HSA path (k_h2d_wait waits for it on the
+  // device) or as a runtime copy on stream ps (the step's stream waits for ev_h2d_)
+  void ingress_copy(u64 step, int is, u64 ptr, u64 len, hipStream_t ps) {
+    IngressSlot& ig = ing_[is];
+    const u64 src = h2d_hsa_ ? ingress_src(ptr) : 0;
+    if (src) {
+      // the slot's last reader (step - INGRESS_SLOTS, collected long ago in the drivers'
+      // order) and its copy are done before the signal is re-armed
+      if (step >= INGRESS_SLOTS && ig.read_issued && hipEventQuery(ig.ev_read) != hipSuccess)
+        HIPCHECK(hipEventSynchronize(ig.ev_read));
+      if (ig.hsa) bounded_wait(ig.sig, -1, "ingress H2D");
+      if (ig.split) bounded_wait(ig.sig2, -1, "ingress H2D");
+      // a large payload in two halves on two engines at once: 56.8 vs 54.9 GB/s on one (the
+      // PCIe link is the bound, bench/micro/h2d_chain_probe.hip, profiles/r6_z/h2d_chain3.txt)
+      const bool split = ing_engine2_ && len >= h2d_split_min_ && len > 8192;
+      const u64 h1 = split ? ((len / 2 + 4095) & ~u64(4095)) : len;
+      hsa_signal_store_relaxed(ig.sig, 1);
+      if (hsa_amd_memory_async_copy_on_engine(ig.buf, gpu_agent_, (const void*)src, cpu_agent_, h1, 0,
+                                              nullptr, ig.sig, ing_engine_, true) != HSA_STATUS_SUCCESS)
+        throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (ingress) failed");
+      if (split) {
+        hsa_signal_store_relaxed(ig.sig2, 1);
+        if (hsa_amd_memory_async_copy_on_engine(ig.buf + h1, gpu_agent_, (const void*)(src + h1), cpu_agent_,
+                                                len - h1, 0, nullptr, ig.sig2, ing_engine2_,
+                                                true) != HSA_STATUS_SUCCESS)
+          throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (ingress, second half) failed");
+      }
+      ig.hsa = true;
+      ig.split = split;
+      return;
+    }
+    if (step >= INGRESS_SLOTS && ig.read_issued && hipEventQuery(ig.ev_read) != hipSuccess)
+      HIPCHECK(hipStreamWaitEvent(ps, ig.ev_read, 0));
+    HIPCHECK(hipMemcpyAsync((void*)ig.buf, (const void*)ptr, len,
+                            sdma_ ? hipMemcpyDeviceToDeviceNoCU : hipMemcpyHostToDevice, ps));
+    ig.hsa = false;
+    ig.split = false;
   }
 
   // Basic.Get requests for the next submitted step (validated by the caller: a local queue
@@ -1313,21 +1294,75 @@ class Engine {
     }
   }
   py::list get_out_py(int p) {
-    const GetOut* go = (const GetOut*)buf("get_out" + std::to_string(p)).ptr;
+    const StepSlot& sp = par(p);
+    const GetOut* go = sp.io.get_out_hh;
     py::list l;
-    for (u32 i = 0; i < nget_[p]; ++i) l.append(py::make_tuple(go[i].status, go[i].msg_count));
+    for (u32 i = 0; i < sp.nget; ++i) l.append(py::make_tuple(go[i].status, go[i].msg_count));
     return l;
+  }
+
+  // ---- deferred control writes (delta_stage.h): staged from any thread while steps run,
+  // carried by the next submitted step.  Here only what needs the engine: names and limits
+  void stage_write_buf(const std::string& name, py::buffer data, size_t offset) {
+    py::buffer_info info = data.request();
+    const size_t n = (size_t)info.size * info.itemsize;
+    const Buf& b = buf(name);
+    if (offset + n > b.bytes) throw std::runtime_error("stage_write overflows " + name);
+    if (b.host) { memcpy((u8*)b.ptr + offset, info.ptr, n); return; }   // host-mapped: direct
+    dl_.stage_write((u64)b.ptr + offset, (const u8*)info.ptr, n);
+  }
+  void stage_mark_dirty(u32 ch) {
+    if (ch >= d_.c_max * d_.chpc) throw std::runtime_error("stage_mark_dirty: bad channel slot");
+    dl_.stage_mark_dirty(ch);
+  }
+  void stage_unpause(u32 conn) {
+    if (conn >= d_.c_max) throw std::runtime_error("stage_unpause: bad connection");
+    dl_.stage_unpause(conn);
+  }
+  void stage_begin() { dl_.stage_begin(); }
+  void stage_end() { dl_.stage_end(); }
+  u64 dl_state(int which) { return dl_.dl_state(which); }
+  py::tuple deltas_pending() {
+    size_t nrec, nd;
+    u64 nbytes;
+    dl_.deltas_pending(&nrec, &nbytes, &nd);
+    return py::make_tuple(nrec, nbytes, nd);
+  }
+  bool host_work() { return dl_.host_work() || side_queued(); }
+  // from the next submitted step on, every step moves queued bodies in the oldest frac/65536
+  // of the HBM log (past the first `hot` entries of a queue with consumers) to the host
+  // spill ring, at most `budget` bytes a step -- spill() without the pipeline drain; frac 0
+  // stops it.  Any thread.
+  void stage_spill(u32 frac, u32 hot, u32 budget) {
+    if (!d_.spill_bytes) return;
+    std::lock_guard<std::mutex> g(dl_.mu);
+    spill_req_[0] = frac; spill_req_[1] = hot; spill_req_[2] = budget;
+  }
+  // between steps (the control plane holds the engine): apply what is staged now
+  void flush_deltas() {
+    if (!dl_.has_deltas()) return;
+    if (any_inflight()) throw std::runtime_error("flush_deltas() between steps only");
+    sync();
+    while (dl_.has_deltas()) {
+      if (!dl_.pack_deltas(par_[0].dl_h, nullptr, nullptr)) break;
+      hipLaunchKernelGGL(k_apply_deltas, dim3(1), dim3(1024), 0, s_comp_, par_[0].io, par_[0].io.delta_h);
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipStreamSynchronize(s_comp_));
+    }
   }
 
   // second half of submit(): the kernels of the staged step of parity p
   void launch(int p) {
-    if (!staged_[p]) throw std::runtime_error("launch: no staged step of this parity");
-    staged_[p] = false;
-    const int e = slot_of_[p];
+    StepSlot& sp = par(p);
+    if (!sp.staged) throw std::runtime_error("launch: no staged step of this parity");
+    sp.staged = false;
+    const int e = sp.slot;
+    EgressSlot& es = eg_[e];
+    IngressSlot& ig = ing_[sp.launch_seq % INGRESS_SLOTS];
     // egress slot e (last used by step t-EGRESS_SLOTS) drained before this step's kernels
     // overwrite it; waited for only after this step's ingress H2D is queued, so the H2D
     // and the in-flight D2H overlap on their two SDMA engines
-    if (copy_mode_ == 3 && sdma_pending_[e]) { HostTimer t(&ht_[1]); sdma_wait(e); }
+    if (copy_mode_ == 3 && es.sdma_pending) { HostTimer t(&ht_[1]); sdma_wait(e); }
     if (overlap_) {
       // ingest half on s_ing_: after this step's H2D and once parity p's buffers are free
       // (the routing half of step t-2); the routing half on s_comp_ behind it and behind
@@ -1337,106 +1372,427 @@ class Engine {
         run_side(s_comp_);
         HIPCHECK(hipStreamWaitEvent(s_ing_, ev_side_, 0));
       }
-      HIPCHECK(hipStreamWaitEvent(s_ing_, ev_h2d_[p], 0));
-      HIPCHECK(hipStreamWaitEvent(s_ing_, ev_pre_[p], 0));
-      if (rest_issued_[p]) HIPCHECK(hipStreamWaitEvent(s_ing_, ev_rest_[p], 0));
+      HIPCHECK(hipStreamWaitEvent(s_ing_, sp.ev_h2d, 0));
+      HIPCHECK(hipStreamWaitEvent(s_ing_, sp.ev_pre, 0));
+      if (sp.rest_issued) HIPCHECK(hipStreamWaitEvent(s_ing_, sp.ev_rest, 0));
       // control writes: applied between steps -- after the previous step's routing half
-      if (dl_step_[p] && rest_issued_[p ^ 1]) HIPCHECK(hipStreamWaitEvent(s_ing_, ev_rest_[p ^ 1], 0));
+      if (sp.dl_step && par_[p ^ 1].rest_issued) HIPCHECK(hipStreamWaitEvent(s_ing_, par_[p ^ 1].ev_rest, 0));
       {
         HostTimer t(&ht_[2]);
-        if (!graph_ing_[p]) capture_on(s_ing_, &graph_ing_[p], [&] { launch_ingest(s_ing_, io_[p]); });
-        HIPCHECK(hipGraphLaunch(graph_ing_[p], s_ing_));
+        if (!sp.graph_ing) capture(s_ing_, &sp.graph_ing, [&] { launch_ingest(s_ing_, sp.io); });
+        HIPCHECK(hipGraphLaunch(sp.graph_ing, s_ing_));
       }
-      HIPCHECK(hipEventRecord(ev_ing_[p], s_ing_));
-      ing_issued_[p] = true;
-      HIPCHECK(hipStreamWaitEvent(s_comp_, ev_ing_[p], 0));
-      if (d2h_issued_[e]) HIPCHECK(hipStreamWaitEvent(s_comp_, ev_d2h_[e], 0));
+      HIPCHECK(hipEventRecord(sp.ev_ing, s_ing_));
+      HIPCHECK(hipStreamWaitEvent(s_comp_, sp.ev_ing, 0));
+      if (es.d2h_issued) HIPCHECK(hipStreamWaitEvent(s_comp_, es.ev_d2h, 0));
       {
         HostTimer t(&ht_[2]);
-        if (!graph_rest_[p]) capture_on(s_comp_, &graph_rest_[p], [&] { launch_rest(s_comp_, io_[p]); });
-        HIPCHECK(hipGraphLaunch(graph_rest_[p], s_comp_));
+        if (!sp.graph_rest) capture(s_comp_, &sp.graph_rest, [&] { launch_rest(s_comp_, sp.io); });
+        HIPCHECK(hipGraphLaunch(sp.graph_rest, s_comp_));
       }
-      HIPCHECK(hipEventRecord(ev_rest_[p], s_comp_));
-      rest_issued_[p] = true;
-      {   // the ingress slot's last reader: the routing half (segments scanned in place)
-        const int is = (int)(launch_seq_[p] % INGRESS_SLOTS);
-        HIPCHECK(hipEventRecord(ev_ing_slot_[is], s_comp_));
-        ing_slot_issued_[is] = true;
-      }
-      HIPCHECK(hipEventRecord(ev_done_[p], s_comp_));
+      HIPCHECK(hipEventRecord(sp.ev_rest, s_comp_));
+      sp.rest_issued = true;
+      // the ingress slot's last reader: the routing half (segments scanned in place)
+      HIPCHECK(hipEventRecord(ig.ev_read, s_comp_));
+      ig.read_issued = true;
+      HIPCHECK(hipEventRecord(sp.ev_done, s_comp_));
       gated_copy(e);
       if (copy_mode_ == 2) {   // egress D2H right behind the step, sized on the device
         // (measured slower than the host-issued SDMA copy -- CU stores over PCIe stall
         // behind the next step's kernels: 8.7 vs 32.9 M msgs/s, profiles/r4_bench/pre_*)
-        HIPCHECK(hipStreamWaitEvent(s_d2h_, ev_rest_[p], 0));
-        hipLaunchKernelGGL(k_copy_out_dev, dim3(copy_wgs_), dim3(256), 0, s_d2h_, egress_host_dev_[e],
-                           (const u8*)egress_dev_[e], (const Counters*)io_[p].ctr);
-        HIPCHECK(hipEventRecord(ev_d2h_[e], s_d2h_));
-        d2h_issued_[e] = true;
-        eager_d2h_[p] = true;
+        HIPCHECK(hipStreamWaitEvent(s_d2h_, sp.ev_rest, 0));
+        hipLaunchKernelGGL(k_copy_out_dev, dim3(copy_wgs_), dim3(256), 0, s_d2h_, es.host_dev,
+                           (const u8*)es.dev, (const Counters*)sp.io.ctr);
+        HIPCHECK(hipEventRecord(es.ev_d2h, s_d2h_));
+        es.d2h_issued = true;
+        sp.eager_d2h = true;
       }
       return;
     }
     if (side_h_) run_side(s_comp_);
-    if (h2d_hip_[p]) HIPCHECK(hipStreamWaitEvent(s_comp_, ev_h2d_[p], 0));
-    if (d2h_issued_[e]) HIPCHECK(hipStreamWaitEvent(s_comp_, ev_d2h_[e], 0));
+    if (sp.h2d_hip) HIPCHECK(hipStreamWaitEvent(s_comp_, sp.ev_h2d, 0));
+    if (es.d2h_issued) HIPCHECK(hipStreamWaitEvent(s_comp_, es.ev_d2h, 0));
     if (d_.world > 1 && !xfer_set_) throw std::runtime_error("set_xfer_buffers() before the first sharded step");
     if (graph_enabled_) {
-      if (!graph_exec_[p]) capture_main(p);
+      if (!sp.graph_exec) capture(s_comp_, &sp.graph_exec, [&] { launch_main(s_comp_, sp.io); });
       HostTimer t(&ht_[2]);
-      HIPCHECK(hipGraphLaunch(graph_exec_[p], s_comp_));
+      HIPCHECK(hipGraphLaunch(sp.graph_exec, s_comp_));
     } else {
-      launch_main(s_comp_, io_[p]);
+      launch_main(s_comp_, sp.io);
     }
     if (d_.world == 1) {   // the ingress slot's last reader (a later prefetch into it waits for it)
-      const int is = (int)(launch_seq_[p] % INGRESS_SLOTS);
-      HIPCHECK(hipEventRecord(ev_ing_slot_[is], s_comp_));
-      ing_slot_issued_[is] = true;
+      HIPCHECK(hipEventRecord(ig.ev_read, s_comp_));
+      ig.read_issued = true;
     }
     if (d_.world > 1 && lag_) {
-      HIPCHECK(hipEventRecord(ev_a_[p], s_comp_));
-      counts_ready_[p] = true;
+      HIPCHECK(hipEventRecord(sp.ev_a, s_comp_));
+      sp.counts_ready = true;
       if (native_x_) {   // the front end runs the previous step's exchange, then launch_b(p)
-        b_due_[p] = true;
+        sp.b_due = true;
         return;
       }
       // phase B right behind phase A: imports the previous step's exchange
-      u32* x = (u32*)buf("xchg" + std::to_string(p)).ptr;
-      for (u32 r = 0; r < d_.world; ++r) {
-        x[2 * WORLD_MAX + r] = x[XC_RECV_AN + r] = lag_recv_.size() == 2 * d_.world ? lag_recv_[r] : 0;
-        x[3 * WORLD_MAX + r] = x[XC_RECV_AB + r] = lag_recv_.size() == 2 * d_.world ? lag_recv_[d_.world + r] : 0;
-      }
+      recv_counts(sp, lag_recv_.size() == 2 * d_.world ? lag_recv_.data() : nullptr);
       lag_recv_.clear();
       if (lag_stream_) {
-        HIPCHECK(hipEventRecord(ev_ext_[p], (hipStream_t)lag_stream_));
-        HIPCHECK(hipStreamWaitEvent(s_comp_, ev_ext_[p], 0));
+        HIPCHECK(hipEventRecord(sp.ev_ext, (hipStream_t)lag_stream_));
+        HIPCHECK(hipStreamWaitEvent(s_comp_, sp.ev_ext, 0));
         lag_stream_ = 0;
       }
-      if (graph_enabled_) {
-        if (!graph_b_[p]) capture_b(p);
-        HIPCHECK(hipGraphLaunch(graph_b_[p], s_comp_));
-      } else {
-        launch_phase_b(s_comp_, io_[p]);
-      }
-      HIPCHECK(hipEventRecord(ev_done_[p], s_comp_));
-      gated_copy(e);
+      run_phase_b(p);
     } else if (d_.world > 1) {
-      HIPCHECK(hipEventRecord(ev_a_[p], s_comp_));
-      phase_a_[p] = true;
-      counts_ready_[p] = true;
+      HIPCHECK(hipEventRecord(sp.ev_a, s_comp_));
+      sp.phase_a = true;
+      sp.counts_ready = true;
     } else {
-      HIPCHECK(hipEventRecord(ev_done_[p], s_comp_));
+      HIPCHECK(hipEventRecord(sp.ev_done, s_comp_));
       gated_copy(e);   // (world 1, one stream: the whole step is one graph)
     }
   }
 
+  // non-blocking: the launched step of parity p has finished (its results are readable)
+  bool step_done(int p) {
+    const StepSlot& sp = par(p);
+    if (!sp.inflight || sp.staged || sp.phase_a || sp.b_due) return !sp.inflight;
+    return hipEventQuery(sp.ev_done) == hipSuccess;
+  }
+
+  void wait_results(int p) {
+    HostTimer ht(&ht_[3]);
+    Range rg("chanamq.step.wait_results");
+    StepSlot& sp = par(p);
+    if (sp.phase_a || sp.b_due) throw std::runtime_error("wait_results: phase B of this sharded step not submitted");
+    if (sp.staged) throw std::runtime_error("wait_results: step staged but never launched");
+    HIPCHECK(hipEventSynchronize(sp.ev_done));
+    sp.inflight = false;
+    if (sp.h2d_addr) {   // (k_h2d_wait gives up after its poll budget: the step then ran on a stale slot)
+      if (*(volatile const i64*)sp.h2d_addr != 0 || (sp.h2d_addr2 && *(volatile const i64*)sp.h2d_addr2 != 0)) {
+        wait_failed_ = true;
+        throw std::runtime_error("ingress copy of step " + std::to_string(sp.launch_seq) +
+                                 " did not complete before its step ran (HSA SDMA copy lost)");
+      }
+    }
+    // egress history of the gated copies' sizing (every finished step, idle ones too)
+    const u64 n = sp.io.ctr_host_h->egress_bytes;
+    eg_hist_[eg_hist_i_++ & 3] = n;
+    eg_stats_[3] += n;
+  }
+
+  void sync() {
+    HIPCHECK(hipStreamSynchronize(s_h2d_));
+    if (s_h2d_alt_) HIPCHECK(hipStreamSynchronize(s_h2d_alt_));
+    HIPCHECK(hipStreamSynchronize(s_pre_));
+    HIPCHECK(hipStreamSynchronize(s_ing_));
+    HIPCHECK(hipStreamSynchronize(s_comp_));
+    HIPCHECK(hipStreamSynchronize(s_d2h_));
+  }
+
+  // seconds spent in each host phase since the last reset
+  py::dict host_times(bool reset) {
+    // (asynchronous exchange: "exchange" is the stepper's wait for the previous job,
+    // "exchange_thread" and "exchange_counts" the exchange thread's time)
+    static const char* names[9] = {"submit", "submit_sdma_wait", "submit_graph_launch", "wait_results",
+                                   "egress_copy", "egress_wait", "exchange", "exchange_counts", "exchange_thread"};
+    py::dict o;
+    for (int i = 0; i < 9; ++i) { o[names[i]] = ht_[i]; if (reset) ht_[i] = 0; }
+    return o;
+  }
+
+  py::dict counters(int p) {
+    const Counters& c = *par(p).io.ctr_host_h;
+    py::dict o;
+#define F(x) o[#x] = c.x
+    F(n_cmds); F(n_frags); F(n_pubs); F(n_acks); F(n_ctrl); F(ctrl_bytes); F(n_pairs); F(n_deliv);
+    F(egress_bytes); F(n_returns); F(n_confirm_frames); F(n_freed); F(n_requeue); F(n_unroutable);
+    F(n_dropped_nomem); F(n_expired); F(n_routed_msgs); F(n_unknown_exchange); F(n_ring_full);
+    F(n_acked); F(log_head); F(log_tail); F(msg_free_top); F(n_live_msgs);
+    F(n_persist); F(n_consumed); F(persist_used); F(n_persist_overflow);
+    F(live_bytes); F(n_grow); F(n_dget); F(spill_moved); F(n_ref); F(gath_off); F(ref_bytes);
+#undef F
+    std::vector<u32> lat(c.lat_hist, c.lat_hist + LAT_BINS);
+    o["lat_hist"] = lat;
+    return o;
+  }
+
+  // ------------------------------------------------------------- egress
+  u64 egress_copy(int p) {
+    HostTimer ht(&ht_[4]);
+    Range rg("chanamq.K5.egress_d2h");
+    StepSlot& sp = par(p);
+    const u64 n = sp.io.ctr_host_h->egress_bytes;
+    const int e = sp.slot;
+    EgressSlot& es = eg_[e];
+    if (es.spec) {   // gated: the bulk is on its way already; the host only adds a tail
+      if (n > es.spec) {
+        const u64 off = es.spec;
+        hsa_signal_store_screlease(es.tail_sig, 1);
+        hsa_status_t st = hsa_amd_memory_async_copy_on_engine((u8*)es.host + off, cpu_agent_,
+                                                              (u8*)es.dev + off, gpu_agent_, n - off, 0, nullptr,
+                                                              es.tail_sig, tail_engine_, true);
+        if (st != HSA_STATUS_SUCCESS) {
+          hsa_signal_store_screlease(es.tail_sig, 0);
+          throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (egress tail) failed");
+        }
+        es.tail_pending = true;
+        ++eg_stats_[1];
+      }
+      return n;
+    }
+    if (sp.eager_d2h) {   // already queued behind the step (launch)
+      sp.eager_d2h = false;
+      return n;
+    }
+    HIPCHECK(hipStreamWaitEvent(s_d2h_, sp.ev_done, 0));
+    if (n && copy_mode_ == 3) {
+      HIPCHECK(hipEventSynchronize(sp.ev_done));
+      // sdma_split 2: large egress split over two SDMA engines, each part decrementing the
+      // slot's signal once (measured slower on MI355X: 28.9 vs 38.6 M msgs/s, p99 6.6 ms,
+      // profiles/r4_sdma_split.md -- off by default)
+      const int k = (n >= (2u << 20) && sdma_engine2_) ? 2 : 1;
+      hsa_signal_store_screlease(es.sdma_sig, k);
+      const u64 half = k == 2 ? ((n / 2) & ~(u64)4095) : n;
+      for (int i = 0; i < k; ++i) {
+        const u64 off = i ? half : 0, len = i ? n - half : half;
+        hsa_status_t st = hsa_amd_memory_async_copy_on_engine(
+            (u8*)es.host + off, cpu_agent_, (u8*)es.dev + off, gpu_agent_, len, 0, nullptr,
+            es.sdma_sig, i ? sdma_engine2_ : sdma_engine_, true);
+        if (st != HSA_STATUS_SUCCESS) throw std::runtime_error("hsa_amd_memory_async_copy_on_engine failed");
+      }
+      es.sdma_pending = true;
+      return n;
+    }
+    if (n && copy_mode_ == 2)
+      hipLaunchKernelGGL(k_copy_out, dim3(copy_wgs_), dim3(256), 0, s_d2h_, es.host_dev,
+                         (const u8*)es.dev, n);
+    else if (n)
+      HIPCHECK(hipMemcpyAsync(es.host, es.dev, n,
+                              sdma_ ? hipMemcpyDeviceToDeviceNoCU : hipMemcpyDeviceToHost, s_d2h_));
+    HIPCHECK(hipEventRecord(es.ev_d2h, s_d2h_));
+    es.d2h_issued = true;
+    return n;
+  }
+
+  void egress_wait(int p) { egress_wait_slot(par(p).slot); }
+
+  // the slot's D2H (+ its tail) complete
+  void sdma_wait(int e) {
+    EgressSlot& es = eg_[e];
+    if (es.sdma_pending) bounded_wait(es.sdma_sig, e, "egress D2H");
+    if (es.tail_pending) bounded_wait(es.tail_sig, e, "egress tail D2H");
+    es.sdma_pending = es.tail_pending = false;
+  }
+
+  // a copy's completion signal reaching 0: an active spin first (a step's egress lands
+  // within its period; a blocked wait would add the interrupt wake-up to every delivery's
+  // latency), then blocked waits up to the engine's wait deadline -- past it the copy is
+  // declared lost: the slot's gate is opened (a gated copy that never saw its step's last
+  // kernel would otherwise hold its SDMA queue forever) and the engine reports an error
+  // (the front end's healthy() turns false, a sharded node fails over).  Was: an unbounded
+  // active wait, a core spinning forever on a lost gate (VERDICT r5 weak 6)
+  void bounded_wait(hsa_signal_t sig, int e, const char* what) {
+    if (hsa_signal_wait_scacquire(sig, HSA_SIGNAL_CONDITION_EQ, 0, spin_ticks_, HSA_WAIT_STATE_ACTIVE) == 0) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    while (hsa_signal_wait_scacquire(sig, HSA_SIGNAL_CONDITION_EQ, 0, block_ticks_, HSA_WAIT_STATE_BLOCKED) != 0) {
+      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(wait_ms_)) {
+        if (e >= 0 && eg_[e].gate_sig.handle) hsa_signal_store_screlease(eg_[e].gate_sig, 0);
+        wait_failed_ = true;
+        throw std::runtime_error(std::string(what) + " of egress slot " + std::to_string(e) + " did not complete within " +
+                                 std::to_string(wait_ms_) + " ms (gate never opened / copy lost)");
+      }
+    }
+  }
+  // fault injection (tests): the next submitted step's egress gate is never opened by its
+  // last kernel (it stores to a scratch word instead), as after a step that died before it
+  void inject_gate_fault() { gate_fault_ = true; }
+  // (tests) the next step's ingress wait polls a word that never reaches 0 (HSA ingress only)
+  void inject_h2d_fault() { h2d_fault_ = true; }
+  bool wait_failed() const { return wait_failed_; }
+
+  // gated egress: bytes to copy speculatively for the next step -- the largest of the last
+  // four steps' egress + 1/16 + 64 KB, in 64 KB units (0 after four steps without egress)
+  u64 spec_bytes() const {
+    u64 mx = 0;
+    for (u64 v : eg_hist_) mx = v > mx ? v : mx;
+    if (!mx) return 0;
+    const u64 sz = (mx + mx / 16 + (64u << 10) + 65535) & ~(u64)65535;
+    return sz < egress_alloc_ ? sz : egress_alloc_;
+  }
+  // gated egress counters: [gated copies, tail copies, bytes copied speculatively, bytes rendered]
+  py::dict egress_stats() const {
+    py::dict o;
+    o["gated"] = gated_;
+    o["gated_copies"] = eg_stats_[0];
+    o["tail_copies"] = eg_stats_[1];
+    o["spec_bytes"] = eg_stats_[2];
+    o["egress_bytes"] = eg_stats_[3];
+    return o;
+  }
+
+  // egress slot (host view "egress_host<slot>") of the step last submitted with parity p
+  int egress_slot(int p) { return par(p).slot; }
+  // egress by reference from the next submitted step on (StepIn.ref_back): bodies of the
+  // last `back` steps' ingress payloads (-1: off; -2: only bodies in the host spill ring) of
+  // at least min_bytes are not rendered;
+  // the caller keeps those payloads unchanged until the delivering step's egress is sent
+  void set_egress_ref(int back, u32 min_bytes) {
+    if (back > 64) throw std::runtime_error("set_egress_ref: at most 64 steps back");
+    ref_back_ = back == -2 ? -2 : back < 0 ? -1 : back;
+    ref_min_ = min_bytes < 16 ? 16 : min_bytes;
+  }
+  // store-record slot (host views "persist<slot>" / "consumed<slot>") of that step
+  int persist_slot(int p) { return par(p).pslot; }
+  const u8* pslot_host(int p) { return persist_h_[par(p).pslot]; }   // (null without persistence)
+  const ConsumedRec* cslot_host(int p) { return consumed_h_[par(p).pslot]; }
+
+  // egress_wait_slot without touching engine state (any thread; the slot's D2H was
+  // issued before the caller learnt of the slot)
+  void egress_ready(int e) {
+    EgressSlot& es = eg_[e];
+    if (copy_mode_ == 3) {
+      if (es.sdma_pending) bounded_wait(es.sdma_sig, e, "egress D2H");
+      if (es.tail_pending) bounded_wait(es.tail_sig, e, "egress tail D2H");
+      return;
+    }
+    if (es.d2h_issued) HIPCHECK(hipEventSynchronize(es.ev_d2h));
+  }
+
+  void egress_wait_slot(int e) {
+    HostTimer ht(&ht_[5]);
+    if (copy_mode_ == 3) { sdma_wait(e); return; }
+    if (eg_[e].d2h_issued) HIPCHECK(hipEventSynchronize(eg_[e].ev_d2h));
+  }
+
+  // the egress D2H of slot e, queued now: starts when the step's last kernel opens the gate
+  void gated_copy(int e) {
+    EgressSlot& es = eg_[e];
+    if (!es.spec) return;
+    Range rg("chanamq.K5.egress_gated");
+    // sdma_split 2: the speculative copy in two halves on two SDMA engines, both released by
+    // the same gate, each decrementing the slot's completion signal once
+    const u64 n = es.spec;
+    const int k = (sdma_split_ > 1 && sdma_engine2_ && n >= (4u << 20)) ? 2 : 1;
+    const u64 half = k == 2 ? ((n / 2) & ~(u64)4095) : n;
+    hsa_signal_store_screlease(es.sdma_sig, k);
+    for (int i = 0; i < k; ++i) {
+      const u64 off = i ? half : 0, len = i ? n - half : half;
+      hsa_status_t st = hsa_amd_memory_async_copy_on_engine((u8*)es.host + off, cpu_agent_,
+                                                            (u8*)es.dev + off, gpu_agent_, len, 1,
+                                                            &es.gate_sig, es.sdma_sig,
+                                                            i ? sdma_engine2_ : sdma_engine_, true);
+      if (st != HSA_STATUS_SUCCESS) {
+        hsa_signal_store_screlease(es.sdma_sig, 0);
+        throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (gated egress) failed");
+      }
+    }
+    es.sdma_pending = true;
+    ++eg_stats_[0];
+    eg_stats_[2] += es.spec;
+  }
+
+  // non-blocking: egress slot e's D2H (and tail) landed in host memory
+  bool egress_done_slot(int e) {
+    EgressSlot& es = eg_[e];
+    if (copy_mode_ == 3) {
+      if (es.sdma_pending && hsa_signal_load_scacquire(es.sdma_sig) != 0) return false;
+      if (es.tail_pending && hsa_signal_load_scacquire(es.tail_sig) != 0) return false;
+      es.sdma_pending = es.tail_pending = false;
+      return true;
+    }
+    return !es.d2h_issued || hipEventQuery(es.ev_d2h) == hipSuccess;
+  }
+
+  // HSA agents of this device and of the host, an SDMA engine for GPU -> host copies
+  void init_sdma() {
+    if (hsa_init() != HSA_STATUS_SUCCESS) throw std::runtime_error("hsa_init failed");
+    struct Ctx { std::vector<hsa_agent_t> gpus, cpus; } ctx;
+    hsa_iterate_agents([](hsa_agent_t a, void* data) {
+      hsa_device_type_t t;
+      hsa_agent_get_info(a, HSA_AGENT_INFO_DEVICE, &t);
+      auto* c = (Ctx*)data;
+      if (t == HSA_DEVICE_TYPE_GPU) c->gpus.push_back(a);
+      else if (t == HSA_DEVICE_TYPE_CPU) c->cpus.push_back(a);
+      return HSA_STATUS_SUCCESS;
+    }, &ctx);
+    if ((int)ctx.gpus.size() <= device_ || ctx.cpus.empty()) throw std::runtime_error("HSA agents not found");
+    {   // bounded_wait: spin 2 ms actively, then block in 1 ms slices
+      u64 f = 0;
+      if (hsa_system_get_info(HSA_SYSTEM_INFO_TIMESTAMP_FREQUENCY, &f) != HSA_STATUS_SUCCESS || !f) f = 100000000ull;
+      spin_ticks_ = f / 500;
+      block_ticks_ = f / 1000;
+    }
+    gpu_agent_ = ctx.gpus[device_];
+    cpu_agent_ = ctx.cpus[0];
+    uint32_t mask = 0;
+    if (hsa_amd_memory_copy_engine_status(cpu_agent_, gpu_agent_, &mask) != HSA_STATUS_SUCCESS || !mask)
+      throw std::runtime_error("no SDMA engine available for device -> host copies");
+    // not the engine of the runtime's own H2D copies: one SDMA engine serialises both
+    // directions (measured 54 GB/s total vs 94 GB/s on two engines, bench/pcie_probe.hip)
+    // (measured on MI355X: engines 0-3 reach PCIe rate, 8 and 15 a third of it)
+    u32 pick = 0;
+    if (sdma_pref_ >= 0 && (mask >> sdma_pref_) & 1u) pick = (u32)sdma_pref_;
+    else if ((mask >> 1) & 1u) pick = 1;
+    else while (!((mask >> pick) & 1u)) ++pick;
+    sdma_engine_ = (hsa_amd_sdma_engine_id_t)(1u << pick);
+    // a second engine for split egress copies: another full-rate one (0-3), not engine 0
+    // (the runtime's H2D engine) when there is a choice
+    sdma_engine2_ = (hsa_amd_sdma_engine_id_t)0;
+    if (sdma_split_ > 1)
+      for (u32 c : {2u, 3u, 0u})
+        if (c != pick && ((mask >> c) & 1u)) { sdma_engine2_ = (hsa_amd_sdma_engine_id_t)(1u << c); break; }
+    // the tail engine (gated egress): another full-rate engine than the gated copies' --
+    // which can sit behind the next step's gate -- and than the runtime's H2D engine 0
+    // (nor the split copies' second engine: an engine's queue is in order, and a gated copy
+    // waiting there for the next step's gate would hold the tail back by a step)
+    tail_engine_ = sdma_engine_;
+    for (u32 c : {2u, 3u, 0u})
+      if (c != pick && ((mask >> c) & 1u) && (1u << c) != (u32)sdma_engine2_) {
+        tail_engine_ = (hsa_amd_sdma_engine_id_t)(1u << c);
+        break;
+      }
+    // the ingress engine (cfg h2d_hsa): engine 0, the runtime's own H2D engine -- the egress
+    // engines stay free of it (measured: egress on engine 0 next to the ingress copies halves
+    // the throughput, profiles/r6_x); else any full-rate engine the egress does not use
+    ing_engine_ = (hsa_amd_sdma_engine_id_t)0;
+    for (u32 c : {0u, 3u, 2u, 1u})
+      if (((mask >> c) & 1u) && (1u << c) != (u32)sdma_engine_ && (1u << c) != (u32)sdma_engine2_ &&
+          (1u << c) != (u32)tail_engine_) {
+        ing_engine_ = (hsa_amd_sdma_engine_id_t)(1u << c);
+        break;
+      }
+    if (!ing_engine_) ing_engine_ = tail_engine_;
+    // a split payload's second engine (cfg h2d_split, default off): another full-rate one the
+    // egress does not use
+    ing_engine2_ = (hsa_amd_sdma_engine_id_t)0;
+    if (h2d_split_cfg_)
+      for (u32 c : {3u, 2u})
+        if (((mask >> c) & 1u) && (1u << c) != (u32)ing_engine_ && (1u << c) != (u32)sdma_engine_ &&
+            (1u << c) != (u32)sdma_engine2_ && (1u << c) != (u32)tail_engine_) {
+          ing_engine2_ = (hsa_amd_sdma_engine_id_t)(1u << c);
+          break;
+        }
+    for (EgressSlot& es : eg_)
+      if (hsa_signal_create(0, 0, nullptr, &es.sdma_sig) != HSA_STATUS_SUCCESS ||
+          hsa_signal_create(0, 0, nullptr, &es.tail_sig) != HSA_STATUS_SUCCESS ||
+          hsa_signal_create(0, 0, nullptr, &es.gate_sig) != HSA_STATUS_SUCCESS)
+        throw std::runtime_error("hsa_signal_create failed");
+  }
+
+  void drain_egress() {
+    for (int e = 0; e < EGRESS_SLOTS; ++e) {
+      sdma_wait(e);
+      if (eg_[e].d2h_issued) HIPCHECK(hipEventSynchronize(eg_[e].ev_d2h));
+    }
+  }
+
+  // ------------------------------------------------------------- exchange driven by the host (Python): send_counts / submit_b / set_import
   // sharded step, after submit(): wait for phase A and return the per-destination send
   // counts [records x world, bytes x world, overflow]
   std::vector<u32> send_counts(int p) {
-    if (!counts_ready_[p]) throw std::runtime_error("send_counts: no phase-A step in flight for this parity");
-    counts_ready_[p] = false;
-    HIPCHECK(hipEventSynchronize(ev_a_[p]));
-    const u32* x = (const u32*)buf("xchg" + std::to_string(p)).ptr;
+    StepSlot& sp = par(p);
+    if (!sp.counts_ready) throw std::runtime_error("send_counts: no phase-A step in flight for this parity");
+    sp.counts_ready = false;
+    HIPCHECK(hipEventSynchronize(sp.ev_a));
+    const u32* x = sp.io.xchg_h;
     std::vector<u32> o;
     for (u32 r = 0; r < d_.world; ++r) o.push_back(x[r]);
     for (u32 r = 0; r < d_.world; ++r) o.push_back(x[WORLD_MAX + r]);
@@ -1447,280 +1803,40 @@ class Engine {
   // sharded step: received [records x world, bytes x world]; the exchange ran on
   // `stream` (0 = already complete); launches phase B behind it
   void submit_b(int p, std::vector<u32> recv, u64 stream) {
-    if (!phase_a_[p]) throw std::runtime_error("submit_b: no phase-A step in flight for this parity");
+    StepSlot& sp = par(p);
+    if (!sp.phase_a) throw std::runtime_error("submit_b: no phase-A step in flight for this parity");
     if (recv.size() != 2 * d_.world) throw std::runtime_error("submit_b: need 2*world counts");
-    u32* x = (u32*)buf("xchg" + std::to_string(p)).ptr;
-    for (u32 r = 0; r < d_.world; ++r) {
-      x[2 * WORLD_MAX + r] = x[XC_RECV_AN + r] = recv[r];
-      x[3 * WORLD_MAX + r] = x[XC_RECV_AB + r] = recv[d_.world + r];
-    }
+    recv_counts(sp, recv.data());
     if (stream) {
-      HIPCHECK(hipEventRecord(ev_ext_[p], (hipStream_t)stream));
-      HIPCHECK(hipStreamWaitEvent(s_comp_, ev_ext_[p], 0));
+      HIPCHECK(hipEventRecord(sp.ev_ext, (hipStream_t)stream));
+      HIPCHECK(hipStreamWaitEvent(s_comp_, sp.ev_ext, 0));
     }
+    run_phase_b(p);
+    sp.phase_a = false;
+  }
+
+  // received counts [records x world, bytes x world] (v null: nothing) into the words phase B
+  // of a host-driven exchange reads (submit_b, exchange_lag's set_import)
+  void recv_counts(StepSlot& sp, const u32* v) {
+    u32* x = sp.io.xchg_h;
+    for (u32 r = 0; r < d_.world; ++r) {
+      x[2 * WORLD_MAX + r] = x[XC_RECV_AN + r] = v ? v[r] : 0;
+      x[3 * WORLD_MAX + r] = x[XC_RECV_AB + r] = v ? v[d_.world + r] : 0;
+    }
+  }
+
+  // phase B of parity p's step, behind whatever s_comp_ was made to wait for: its last kernel
+  // finishes the step and opens the egress gate (sharded ranks gate too)
+  void run_phase_b(int p) {
+    StepSlot& sp = par_[p];
     if (graph_enabled_) {
-      if (!graph_b_[p]) capture_b(p);
-      HIPCHECK(hipGraphLaunch(graph_b_[p], s_comp_));
+      if (!sp.graph_b) capture(s_comp_, &sp.graph_b, [&] { launch_phase_b(s_comp_, sp.io); });
+      HIPCHECK(hipGraphLaunch(sp.graph_b, s_comp_));
     } else {
-      launch_phase_b(s_comp_, io_[p]);
+      launch_phase_b(s_comp_, sp.io);
     }
-    HIPCHECK(hipEventRecord(ev_done_[p], s_comp_));
-    gated_copy(slot_of_[p]);   // (the phase-B render opens the gate)
-    phase_a_[p] = false;
-  }
-
-  // recovery: enqueue store records (RDesc with MF_RESTORE, payload [ex][rk][props][body])
-  // through the import path, between steps; returns the number of messages enqueued
-  // cold bodies to the host spill ring, between steps: every queued message past the first
-  // `hot` entries of its queue whose slot lies below log position `lim` (k_spill); returns
-  // the bytes moved (the log tail advances over the emptied blocks at the next step)
-  u64 spill(u64 lim, u32 hot) {
-    if (!d_.spill_bytes) return 0;
-    if (inflight_[0] || inflight_[1]) throw std::runtime_error("spill() between steps only");
-    if (native_x_ && (counts_ready_[0] || counts_ready_[1])) throw std::runtime_error("spill() with an exchange pending");
-    Range rg("chanamq.spill");
-    sync();
-    HIPCHECK(hipMemsetAsync(spill_moved_, 0, 8, s_comp_));
-    hipLaunchKernelGGL(k_spill, dim3(d_.q_max), dim3(256), 0, s_comp_, io_[0], lim, hot, spill_moved_);
-    HIPCHECK(hipGetLastError());
-    unsigned long long moved = 0;
-    HIPCHECK(hipMemcpyAsync(&moved, spill_moved_, 8, hipMemcpyDeviceToHost, s_comp_));
-    HIPCHECK(hipStreamSynchronize(s_comp_));
-    return moved;
-  }
-
-  // ---- cold store (third body tier), between steps; the host moves the bytes
-  // out: candidate records (ColdRec[], bytes 0 = skip) for the host to write to the store
-  // (slots below spill tail + lim)
-  py::bytes cold_pick(u32 hot, u64 lim, u32 max_n, u64 max_bytes) {
-    if (!d_.spill_bytes) return py::bytes("");
-    cold_guard("cold_pick");
-    if (max_n > COLD_BATCH) max_n = COLD_BATCH;
-    HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s_comp_));
-    HIPCHECK(hipMemsetAsync(cold_bytes_, 0, 8, s_comp_));
-    hipLaunchKernelGGL(k_cold_pick, dim3(d_.q_max), dim3(256), 0, s_comp_, io_[0], hot, lim, (u64)0, cold_recs_,
-                       max_n, cold_cnt_, cold_bytes_, max_bytes);
-    return cold_fetch(max_n);
-  }
-  // ... the host stored them (ColdRec.cold = store offsets): switch the messages over
-  void cold_commit(py::buffer recs) {
-    const u32 n = cold_upload(recs);
-    if (n) hipLaunchKernelGGL(k_cold_commit, blocks(n, 256), dim3(256), 0, s_comp_, io_[0], cold_recs_, n);
-    HIPCHECK(hipStreamSynchronize(s_comp_));
-  }
-  // in: the cold entries near the heads of the held queues, each with a spill-ring slot
-  py::bytes cold_scan(u32 window, u32 max_n) {
-    if (!d_.spill_bytes) return py::bytes("");
-    cold_guard("cold_scan");
-    if (max_n > COLD_BATCH) max_n = COLD_BATCH;
-    HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s_comp_));
-    HIPCHECK(hipMemsetAsync(cold_end_, 0, 8ull * d_.q_max, s_comp_));
-    hipLaunchKernelGGL(k_cold_scan, dim3(d_.q_max), dim3(64), 0, s_comp_, io_[0], window, cold_recs_, max_n, cold_cnt_,
-                       cold_end_);
-    return cold_fetch(max_n);
-  }
-  // ... the host read their bodies into those slots: back to SPILL_BIT, q_cold_lim moved on
-  void cold_in(py::buffer recs) {
-    const u32 n = cold_upload(recs);
-    const u64 g = n > d_.q_max ? n : d_.q_max;
-    hipLaunchKernelGGL(k_cold_in, blocks(g, 256), dim3(256), 0, s_comp_, io_[0], cold_recs_, n, cold_end_);
-    HIPCHECK(hipStreamSynchronize(s_comp_));
-  }
-  // ---- the same four operations beside the steps (no pipeline drain, single GPU): the
-  // cold thread posts one (side_*), the next launch() runs it on the compute stream between
-  // two steps, side_wait() hands back its records; the steps keep flowing while the host
-  // moves bodies between the ring and the store.  A pick is picked up again by the commit
-  // only where its entry is still queued (k_cold_commit); k_cold_scan's ring slots count as
-  // live until k_cold_in.  SIDE_LIVE copies cold_live (store segment GC).
-  enum : int { SIDE_NONE = 0, SIDE_PICK, SIDE_COMMIT, SIDE_SCAN, SIDE_IN, SIDE_LIVE };
-  void side_post(int kind, u32 a, u64 b, u64 c, u32 max_n, u64 max_bytes, const ColdRec* recs, u32 n) {
-    if (d_.world != 1) throw std::runtime_error("side operations: single-GPU engines only");
-    if (!side_h_) throw std::runtime_error("side operations: no spill ring");
-    std::lock_guard<std::mutex> g(side_mu_);
-    if (side_.kind) throw std::runtime_error("side operation pending (side_wait first)");
-    if (n) memcpy((u8*)side_h_ + 64, recs, sizeof(ColdRec) * n);
-    side_ = Side{kind, a, b, c, max_n > COLD_BATCH ? COLD_BATCH : max_n, max_bytes, n, false};
-  }
-  void side_cold_pick(u32 hot, u64 lim_rel, u64 min_used, u32 max_n, u64 max_bytes) {
-    side_post(SIDE_PICK, hot, lim_rel, min_used, max_n, max_bytes, nullptr, 0);
-  }
-  void side_cold_scan(u32 window, u32 max_n) { side_post(SIDE_SCAN, window, 0, 0, max_n, 0, nullptr, 0); }
-  void side_cold_commit(py::buffer recs) { side_recs(SIDE_COMMIT, recs); }
-  void side_cold_in(py::buffer recs) { side_recs(SIDE_IN, recs); }
-  void side_cold_live() { side_post(SIDE_LIVE, 0, 0, 0, 0, 0, nullptr, 0); }
-  void side_recs(int kind, py::buffer recs) {
-    py::buffer_info bi = recs.request();
-    const size_t nb = (size_t)bi.size * bi.itemsize;
-    if (nb % sizeof(ColdRec) || nb / sizeof(ColdRec) > COLD_BATCH) throw std::runtime_error("cold: bad ColdRec batch");
-    side_post(kind, 0, 0, 0, 0, 0, (const ColdRec*)bi.ptr, (u32)(nb / sizeof(ColdRec)));
-  }
-  bool side_pending() {
-    std::lock_guard<std::mutex> g(side_mu_);
-    return side_.kind != SIDE_NONE;
-  }
-  bool side_queued() {
-    std::lock_guard<std::mutex> g(side_mu_);
-    return side_.kind && !side_.launched;
-  }
-  // launch(): the posted operation on stream s, ahead of the step's kernels
-  void run_side(hipStream_t s) {
-    std::lock_guard<std::mutex> g(side_mu_);
-    if (!side_.kind || side_.launched) return;
-    ColdRec* hrecs = (ColdRec*)((u8*)side_h_ + 64);
-    ColdRec* drecs = (ColdRec*)((u8*)side_d_ + 64);
-    switch (side_.kind) {
-      case SIDE_PICK:
-      case SIDE_SCAN:
-        HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s));
-        if (side_.kind == SIDE_PICK) {
-          HIPCHECK(hipMemsetAsync(cold_bytes_, 0, 8, s));
-          hipLaunchKernelGGL(k_cold_pick, dim3(d_.q_max), dim3(256), 0, s, io_[0], side_.a, side_.b, side_.c,
-                             cold_recs_, side_.max_n, cold_cnt_, cold_bytes_, side_.max_bytes);
-        } else {
-          HIPCHECK(hipMemsetAsync(cold_end_, 0, 8ull * d_.q_max, s));
-          hipLaunchKernelGGL(k_cold_scan, dim3(d_.q_max), dim3(64), 0, s, io_[0], side_.a, cold_recs_, side_.max_n,
-                             cold_cnt_, cold_end_);
-        }
-        hipLaunchKernelGGL(k_side_out, dim3(64), dim3(256), 0, s, (const ColdRec*)cold_recs_, (const u32*)cold_cnt_,
-                           side_.max_n, (u32*)drecs, (u32*)side_d_);
-        break;
-      case SIDE_COMMIT:
-      case SIDE_IN:
-        if (side_.n)
-          HIPCHECK(hipMemcpyAsync(cold_recs_, hrecs, sizeof(ColdRec) * side_.n, hipMemcpyHostToDevice, s));
-        if (side_.kind == SIDE_COMMIT) {
-          if (side_.n)
-            hipLaunchKernelGGL(k_cold_commit, blocks(side_.n, 256), dim3(256), 0, s, io_[0], cold_recs_, side_.n);
-        } else {
-          const u64 g2 = side_.n > d_.q_max ? side_.n : d_.q_max;
-          hipLaunchKernelGGL(k_cold_in, blocks(g2, 256), dim3(256), 0, s, io_[0], cold_recs_, side_.n, cold_end_);
-        }
-        break;
-      case SIDE_LIVE:
-        HIPCHECK(hipMemcpyAsync(side_live_h_, d_.cold_live, 8ull * COLD_SEGS, hipMemcpyDeviceToHost, s));
-        break;
-    }
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(ev_side_, s));
-    side_.launched = true;
-    side_cv_.notify_all();
-  }
-  // the posted operation's result once it ran: ColdRec[] (pick / scan), cold_live bytes
-  // (live), b"" (commit / in); None while it has not finished within timeout_s
-  py::object side_wait(double timeout_s) {
-    int kind = SIDE_NONE;
-    hipError_t err = hipSuccess;
-    bool done = false;
-    {
-      py::gil_scoped_release nogil;   // (no Python objects in here)
-      std::unique_lock<std::mutex> g(side_mu_);
-      kind = side_.kind;
-      const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds((i64)(timeout_s * 1e6));
-      if (kind && side_cv_.wait_until(g, until, [&] { return side_.launched; })) {
-        g.unlock();
-        while (true) {
-          err = hipEventQuery(ev_side_);
-          if (err == hipSuccess) { done = true; break; }
-          if (err != hipErrorNotReady || std::chrono::steady_clock::now() > until) break;
-          std::this_thread::sleep_for(std::chrono::microseconds(50));
-        }
-      }
-    }
-    if (!kind) throw std::runtime_error("side_wait: nothing posted");
-    if (err != hipSuccess && err != hipErrorNotReady) HIPCHECK(err);
-    if (!done) return py::none();
-    std::lock_guard<std::mutex> g(side_mu_);
-    side_.kind = SIDE_NONE;
-    if (kind == SIDE_PICK || kind == SIDE_SCAN) {
-      const u32 n = *(volatile u32*)side_h_;
-      return py::bytes((const char*)side_h_ + 64, sizeof(ColdRec) * (size_t)n);
-    }
-    if (kind == SIDE_LIVE) return py::bytes((const char*)side_live_h_, 8ull * COLD_SEGS);
-    return py::bytes("");
-  }
-
-  void cold_guard(const char* what) {
-    if (inflight_[0] || inflight_[1]) throw std::runtime_error(std::string(what) + "() between steps only");
-    if (native_x_ && (counts_ready_[0] || counts_ready_[1]))
-      throw std::runtime_error(std::string(what) + "() with an exchange pending");
-    sync();
-  }
-  py::bytes cold_fetch(u32 max_n) {
-    u32 n = 0;
-    HIPCHECK(hipMemcpyAsync(&n, cold_cnt_, 4, hipMemcpyDeviceToHost, s_comp_));
-    HIPCHECK(hipStreamSynchronize(s_comp_));
-    if (n > max_n) n = max_n;
-    std::string out(sizeof(ColdRec) * (size_t)n, '\0');
-    if (n) HIPCHECK(hipMemcpy(&out[0], cold_recs_, out.size(), hipMemcpyDeviceToHost));
-    return py::bytes(out);
-  }
-  u32 cold_upload(py::buffer recs) {
-    py::buffer_info bi = recs.request();
-    const size_t nb = (size_t)bi.size * bi.itemsize;
-    if (nb % sizeof(ColdRec) || nb / sizeof(ColdRec) > COLD_BATCH) throw std::runtime_error("cold: bad ColdRec batch");
-    const u32 n = (u32)(nb / sizeof(ColdRec));
-    if (n) HIPCHECK(hipMemcpy(cold_recs_, bi.ptr, nb, hipMemcpyHostToDevice));
-    return n;
-  }
-
-  u32 restore(py::buffer desc, py::buffer pay, i64 now_ms) {
-    py::buffer_info di = desc.request(), pi = pay.request();
-    u64 db = (u64)di.size * di.itemsize, pb = (u64)pi.size * pi.itemsize;
-    u32 n = (u32)(db / sizeof(RDesc));
-    // native exchange: restores run at a synchronisation point (no import pending) through
-    // parity 0's receive buffers
-    const RDesc* rdesc = d_.recv_desc ? d_.recv_desc : (native_x_ ? io_[0].recv_desc : nullptr);
-    const u8* rpay = d_.recv_pay ? d_.recv_pay : (native_x_ ? io_[0].recv_pay : nullptr);
-    if (!rdesc || n > d_.import_max || pb > d_.xfer_bytes)
-      throw std::runtime_error("restore batch exceeds the import buffers (restore_max / restore_bytes)");
-    if (inflight_[0] || inflight_[1]) throw std::runtime_error("restore() between steps only");
-    if (native_x_ && (counts_ready_[0] || counts_ready_[1]))
-      throw std::runtime_error("restore() with an exchange pending");
-    sync();
-    drain_egress();
-    if (db) HIPCHECK(hipMemcpy((void*)rdesc, di.ptr, db, hipMemcpyHostToDevice));
-    if (pb) HIPCHECK(hipMemcpy((void*)rpay, pi.ptr, pb, hipMemcpyHostToDevice));
-    DS& io = io_[0];
-    StepIn& in = *stage_in_[0];   // (k_stage copies it to the device; no step in flight)
-    in = StepIn{};
-    in.ref_back = 0xffffffffu;   // (no dispatch: nothing rendered)
-    in.nseg = 0;
-    in.now_ms = now_ms;
-    in.step = seq_;
-    in.id_ms = now_ms;
-    in.worker = 0;
-    in.egress = (u64)egress_dev_[0];
-    in.ingress = (u64)ingress_slot_[0];
-    u32* x = (u32*)buf("xchg0").ptr;
-    for (u32 r = 0; r < 2 * WORLD_MAX; ++r) x[2 * WORLD_MAX + r] = x[XC_RECV_AN + r] = 0;
-    for (u32 r = 0; r < WORLD_MAX; ++r) x[XC_RACK_N + r] = 0;
-    x[2 * WORLD_MAX + d_.my_rank] = x[XC_RECV_AN + d_.my_rank] = n;
-    x[3 * WORLD_MAX + d_.my_rank] = x[XC_RECV_AB + d_.my_rank] = (u32)pb;
-    launch_ingest(s_comp_, io);
-    launch_route(s_comp_, io, d_.pub_max);
-    launch_phase_b(s_comp_, io, /*dispatch=*/false);
-    HIPCHECK(hipStreamSynchronize(s_comp_));
-    const Counters* c = (const Counters*)buf("ctr_host0").ptr;
-    return c->n_routed_msgs;
-  }
-
-  // Basic.Get between steps: (status, message_count, frames, tag, msg_id, qpos, persist,
-  // expired [(msg_id, q, qpos)] of durable x persistent messages dropped by the TTL skip)
-  py::tuple basic_get(u32 q, u32 chslot, u32 noack, i64 now_ms) {
-    if (inflight_[0] || inflight_[1]) throw std::runtime_error("basic_get() between steps only");
-    if (q >= d_.q_max || chslot >= d_.c_max * d_.chpc) throw std::runtime_error("basic_get: bad queue / channel");
-    Range rg("chanamq.basic_get");
-    sync();
-    hipLaunchKernelGGL(k_basic_get, dim3(1), dim3(64), 0, s_comp_, io_[0], q, chslot, noack, now_ms, get_out_dev_,
-                       get_cap_, get_res_dev_);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(s_comp_));
-    const GetRes& r = *(const GetRes*)buf("get_res").ptr;
-    py::list exp;
-    for (u32 i = 0; i < r.n_exp && i < GET_EXP_MAX; ++i)
-      exp.append(py::make_tuple(r.exp[i].msg_id, r.exp[i].q, r.exp[i].qpos));
-    py::bytes frames(r.status == GET_OK ? (const char*)buf("get_out").ptr : "", r.status == GET_OK ? r.out_len : 0);
-    return py::make_tuple(r.status, r.msg_count, frames, r.tag, r.msg_id, r.qpos, r.persist, exp);
+    HIPCHECK(hipEventRecord(sp.ev_done, s_comp_));
+    gated_copy(sp.slot);
   }
 
   // exchange_lag mode: the all-to-all of step t finished on `stream` (0 = complete) with
@@ -1733,11 +1849,16 @@ class Engine {
 
   // per-parity exchange operands (exchange_lag: parity p sends from S[p] and imports R[p^1])
   void set_xfer_parity(int p, u64 send_desc, u64 send_pay, u64 recv_desc, u64 recv_pay) {
-    io_[p].send_desc = (RDesc*)send_desc; io_[p].send_pay = (u8*)send_pay;
-    io_[p].recv_desc = (const RDesc*)recv_desc; io_[p].recv_pay = (const u8*)recv_pay;
-    if (graph_exec_[p]) { HIPCHECK(hipGraphExecDestroy(graph_exec_[p])); graph_exec_[p] = nullptr; }
-    if (graph_b_[p]) { HIPCHECK(hipGraphExecDestroy(graph_b_[p])); graph_b_[p] = nullptr; }
+    StepSlot& sp = par(p);
+    sp.io.send_desc = (RDesc*)send_desc; sp.io.send_pay = (u8*)send_pay;
+    sp.io.recv_desc = (const RDesc*)recv_desc; sp.io.recv_pay = (const u8*)recv_pay;
+    drop_graphs(sp);
     xfer_set_ = true;
+  }
+  // (the captured graphs hold the old operands)
+  void drop_graphs(StepSlot& sp) {
+    if (sp.graph_exec) { HIPCHECK(hipGraphExecDestroy(sp.graph_exec)); sp.graph_exec = nullptr; }
+    if (sp.graph_b) { HIPCHECK(hipGraphExecDestroy(sp.graph_b)); sp.graph_b = nullptr; }
   }
 
   // caller-owned exchange operands (device pointers, e.g. torch tensors used by RCCL)
@@ -1745,10 +1866,10 @@ class Engine {
     d_.send_desc = (RDesc*)send_desc; d_.send_pay = (u8*)send_pay;
     d_.recv_desc = (const RDesc*)recv_desc; d_.recv_pay = (const u8*)recv_pay;
     for (int p = 0; p < npar_; ++p) {
-      io_[p].send_desc = d_.send_desc; io_[p].send_pay = d_.send_pay;
-      io_[p].recv_desc = d_.recv_desc; io_[p].recv_pay = d_.recv_pay;
-      if (graph_exec_[p]) { HIPCHECK(hipGraphExecDestroy(graph_exec_[p])); graph_exec_[p] = nullptr; }
-      if (graph_b_[p]) { HIPCHECK(hipGraphExecDestroy(graph_b_[p])); graph_b_[p] = nullptr; }
+      StepSlot& sp = par_[p];
+      sp.io.send_desc = d_.send_desc; sp.io.send_pay = d_.send_pay;
+      sp.io.recv_desc = d_.recv_desc; sp.io.recv_pay = d_.recv_pay;
+      drop_graphs(sp);
     }
     xfer_set_ = true;
   }
@@ -1832,10 +1953,11 @@ class Engine {
   // with nothing to import.
   int exchange(int q, u32 flags, u32* or_flags) {
     if (!native_x_ || (!rccl_ && !shm_)) throw std::runtime_error("exchange: no native exchange set up");
-    if (!counts_ready_[q]) throw std::runtime_error("exchange: no phase-A step of this parity");
+    StepSlot& sq = par(q);
+    if (!sq.counts_ready) throw std::runtime_error("exchange: no phase-A step of this parity");
     if (!async_x_) {
       const int rc = exchange_now(q, flags, or_flags, -1);
-      if (rc == 0) counts_ready_[q] = false;
+      if (rc == 0) sq.counts_ready = false;
       return rc;
     }
     HostTimer ht(&ht_[6]);
@@ -1844,7 +1966,7 @@ class Engine {
     x_collect(&rc, &orf);
     *or_flags = orf;
     if (rc) return rc;
-    counts_ready_[q] = false;
+    sq.counts_ready = false;
     // what the next phase B (parity q^1) imports starts out as nothing: the job writes the
     // counts when it succeeds; a phase B whose wait gives up imports nothing instead of the
     // counts parity q^1 held two steps ago.  (Its last reader, step t-2, has
@@ -1855,7 +1977,7 @@ class Engine {
     xflags_ = flags;
     xseq_job_ = ++xjob_seq_;
     if (xseq_job_ == 0) xseq_job_ = ++xjob_seq_;   // (0: no wait)
-    b_wait_[q ^ 1] = xseq_job_;
+    par_[q ^ 1].b_wait = xseq_job_;
     xjob_ = true;
     xcv_.notify_all();
     return 0;
@@ -1924,13 +2046,13 @@ class Engine {
     if (xth_.joinable()) xth_.join();
     std::lock_guard<std::mutex> g(xmu_);
     xstop_ = xjob_ = xbusy_ = xres_ = false;
-    b_wait_[0] = b_wait_[1] = 0;
+    for (StepSlot& sp : par_) sp.b_wait = 0;
   }
 
   // what phase B of parity p imports: per rank [records, bytes, publish records, publish
   // bytes, link acks]; v null: nothing
   void x_recv_counts(int p, const u32* v) {
-    u32* x = (u32*)buf("xchg" + std::to_string(p)).ptr;
+    u32* x = par_[p].io.xchg_h;
     for (u32 r = 0; r < d_.world; ++r) {
       x[XC_RECV_N + r] = v ? v[r] : 0;
       x[XC_RECV_B + r] = v ? v[d_.world + r] : 0;
@@ -1945,8 +2067,8 @@ class Engine {
   int exchange_now(int q, u32 flags, u32* or_flags, int dst) {
     Range rg("chanamq.X1.exchange");
     HostTimer ht(&ht_[dst >= 0 ? 8 : 6]);   // (async: the exchange thread's time)
-    HIPCHECK(hipEventSynchronize(ev_a_[q]));
-    const u32* x = (const u32*)buf("xchg" + std::to_string(q)).ptr;
+    HIPCHECK(hipEventSynchronize(par_[q].ev_a));
+    const u32* x = par_[q].io.xchg_h;
     if (x[XC_OVF]) throw std::runtime_error("cross-rank send buffers overflowed (xfer_desc_max / xfer_bytes)");
     const int n = (int)xmembers_.size();
     int me = 0;
@@ -1960,7 +2082,7 @@ class Engine {
     }
     // link deliveries / acks of the step before (its phase B preceded this phase A): the
     // other parity's link buffers, destination-major (k_link_bases)
-    const u32* xl = (const u32*)buf("xchg" + std::to_string(q ^ 1)).ptr;
+    const u32* xl = par_[q ^ 1].io.xchg_h;
     u64 lbn[WORLD_MAX], lbb[WORLD_MAX];
     u32 lnn[WORLD_MAX], lnb[WORLD_MAX], lnk[WORLD_MAX];
     {
@@ -2014,15 +2136,15 @@ class Engine {
     }
     if (rn > d_.import_max || rb > d_.import_bytes || (rk && (!links_ || rk > (u64)d_.world * d_.lk_cap)))
       throw std::runtime_error("exchange: received records exceed the import buffers");
-    u8* R_d = xr_desc_[q];
-    u8* R_p = xr_pay_[q];
-    const u8* S_d = xs_desc_[q];
-    const u8* S_p = xs_pay_[q];
+    u8* R_d = par_[q].xr_desc;
+    u8* R_p = par_[q].xr_pay;
+    const u8* S_d = par_[q].xs_desc;
+    const u8* S_p = par_[q].xs_pay;
     // link buffers: sent from the other parity (step t-1), received with this exchange
-    const u8* L_d = links_ ? ls_desc_[q ^ 1] : nullptr;
-    const u8* L_p = links_ ? ls_pay_[q ^ 1] : nullptr;
-    const u8* K_s = links_ ? lk_send_[q ^ 1] : nullptr;
-    u8* RK = links_ ? rack_[q] : nullptr;
+    const u8* L_d = links_ ? par_[q ^ 1].ls_desc : nullptr;
+    const u8* L_p = links_ ? par_[q ^ 1].ls_pay : nullptr;
+    const u8* K_s = links_ ? par_[q ^ 1].lk_send : nullptr;
+    u8* RK = links_ ? par_[q].rack : nullptr;
     if (rccl_) {
       std::vector<std::vector<cmqx::XPart>> snd(n), rcv(n);
       for (int i = 0; i < n; ++i) {
@@ -2127,7 +2249,7 @@ class Engine {
   // A host-run step of the control plane (collect false) leaves the stepper's uncollected
   // result alone: it carries the flags every rank acts on at the same step.
   int drop_exchange(int q, bool collect = true) {
-    counts_ready_[q] = false;
+    par(q).counts_ready = false;
     if (!async_x_) {   // (asynchronous: the exchange thread's job owns no stepper state)
       lag_recv_.clear();
       x_wait_ = false;
@@ -2141,16 +2263,17 @@ class Engine {
 
   // phase B of the launched step of parity p, importing the last exchange (if any)
   void launch_b(int p) {
-    if (!b_due_[p]) throw std::runtime_error("launch_b: no phase-A step of this parity");
-    b_due_[p] = false;
+    StepSlot& sp = par(p);
+    if (!sp.b_due) throw std::runtime_error("launch_b: no phase-A step of this parity");
+    sp.b_due = false;
     if (async_x_) {   // behind its exchange job (the exchange thread writes the counts)
-      const u32 w = b_wait_[p];
-      b_wait_[p] = 0;
+      const u32 w = sp.b_wait;
+      sp.b_wait = 0;
       // give up only well past every bound the job itself has (counts barrier + bulk
       // barrier + the bulk's own wait, each xtimeout_ms) plus settle: then the job is lost
       const u64 lim = ((u64)xtimeout_ms_ * 3 + 5000) * 100000ull;   // s_memrealtime: 100 MHz
       if (w) hipLaunchKernelGGL(k_xwait, dim3(1), dim3(64), 0, s_comp_, (const u32*)xflag_d_, w, xflag_d_ + 1, lim,
-                                io_[p].xchg, d_.world);
+                                sp.io.xchg, d_.world);
       else x_recv_counts(p, nullptr);
     } else {
       x_recv_counts(p, lag_recv_.size() == 5 * d_.world ? lag_recv_.data() : nullptr);
@@ -2158,14 +2281,257 @@ class Engine {
       if (x_wait_ && rccl_) HIPCHECK(hipStreamWaitEvent(s_comp_, rccl_->event(), 0));
       x_wait_ = false;
     }
-    if (graph_enabled_) {
-      if (!graph_b_[p]) capture_b(p);
-      HIPCHECK(hipGraphLaunch(graph_b_[p], s_comp_));
-    } else {
-      launch_phase_b(s_comp_, io_[p]);
+    run_phase_b(p);
+  }
+
+  // ------------------------------------------------------------- side operations (between steps, or beside them)
+  // cold bodies to the host spill ring, between steps: every queued message past the first
+  // `hot` entries of its queue whose slot lies below log position `lim` (k_spill); returns
+  // the bytes moved (the log tail advances over the emptied blocks at the next step)
+  u64 spill(u64 lim, u32 hot) {
+    if (!d_.spill_bytes) return 0;
+    Range rg("chanamq.spill");
+    between_steps("spill");
+    HIPCHECK(hipMemsetAsync(spill_moved_, 0, 8, s_comp_));
+    hipLaunchKernelGGL(k_spill, dim3(d_.q_max), dim3(256), 0, s_comp_, par_[0].io, lim, hot, spill_moved_);
+    HIPCHECK(hipGetLastError());
+    unsigned long long moved = 0;
+    HIPCHECK(hipMemcpyAsync(&moved, spill_moved_, 8, hipMemcpyDeviceToHost, s_comp_));
+    HIPCHECK(hipStreamSynchronize(s_comp_));
+    return moved;
+  }
+
+  // ---- cold store (third body tier), between steps; the host moves the bytes
+  // out: candidate records (ColdRec[], bytes 0 = skip) for the host to write to the store
+  // (slots below spill tail + lim)
+  py::bytes cold_pick(u32 hot, u64 lim, u32 max_n, u64 max_bytes) {
+    if (!d_.spill_bytes) return py::bytes("");
+    between_steps("cold_pick");
+    if (max_n > COLD_BATCH) max_n = COLD_BATCH;
+    HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s_comp_));
+    HIPCHECK(hipMemsetAsync(cold_bytes_, 0, 8, s_comp_));
+    hipLaunchKernelGGL(k_cold_pick, dim3(d_.q_max), dim3(256), 0, s_comp_, par_[0].io, hot, lim, (u64)0, cold_recs_,
+                       max_n, cold_cnt_, cold_bytes_, max_bytes);
+    return cold_fetch(max_n);
+  }
+  // ... the host stored them (ColdRec.cold = store offsets): switch the messages over
+  void cold_commit(py::buffer recs) {
+    const u32 n = cold_upload(recs);
+    if (n) hipLaunchKernelGGL(k_cold_commit, blocks(n, 256), dim3(256), 0, s_comp_, par_[0].io, cold_recs_, n);
+    HIPCHECK(hipStreamSynchronize(s_comp_));
+  }
+  // in: the cold entries near the heads of the held queues, each with a spill-ring slot
+  py::bytes cold_scan(u32 window, u32 max_n) {
+    if (!d_.spill_bytes) return py::bytes("");
+    between_steps("cold_scan");
+    if (max_n > COLD_BATCH) max_n = COLD_BATCH;
+    HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s_comp_));
+    HIPCHECK(hipMemsetAsync(cold_end_, 0, 8ull * d_.q_max, s_comp_));
+    hipLaunchKernelGGL(k_cold_scan, dim3(d_.q_max), dim3(64), 0, s_comp_, par_[0].io, window, cold_recs_, max_n, cold_cnt_,
+                       cold_end_);
+    return cold_fetch(max_n);
+  }
+  // ... the host read their bodies into those slots: back to SPILL_BIT, q_cold_lim moved on
+  void cold_in(py::buffer recs) {
+    const u32 n = cold_upload(recs);
+    const u64 g = n > d_.q_max ? n : d_.q_max;
+    hipLaunchKernelGGL(k_cold_in, blocks(g, 256), dim3(256), 0, s_comp_, par_[0].io, cold_recs_, n, cold_end_);
+    HIPCHECK(hipStreamSynchronize(s_comp_));
+  }
+  // ---- the same four operations beside the steps (no pipeline drain, single GPU): the
+  // cold thread posts one (side_*), the next launch() runs it on the compute stream between
+  // two steps, side_wait() hands back its records; the steps keep flowing while the host
+  // moves bodies between the ring and the store.  A pick is picked up again by the commit
+  // only where its entry is still queued (k_cold_commit); k_cold_scan's ring slots count as
+  // live until k_cold_in.  SIDE_LIVE copies cold_live (store segment GC).
+  enum : int { SIDE_NONE = 0, SIDE_PICK, SIDE_COMMIT, SIDE_SCAN, SIDE_IN, SIDE_LIVE };
+  void side_post(int kind, u32 a, u64 b, u64 c, u32 max_n, u64 max_bytes, const ColdRec* recs, u32 n) {
+    if (d_.world != 1) throw std::runtime_error("side operations: single-GPU engines only");
+    if (!side_h_) throw std::runtime_error("side operations: no spill ring");
+    std::lock_guard<std::mutex> g(side_mu_);
+    if (side_.kind) throw std::runtime_error("side operation pending (side_wait first)");
+    if (n) memcpy((u8*)side_h_ + 64, recs, sizeof(ColdRec) * n);
+    side_ = Side{kind, a, b, c, max_n > COLD_BATCH ? COLD_BATCH : max_n, max_bytes, n, false};
+  }
+  void side_cold_pick(u32 hot, u64 lim_rel, u64 min_used, u32 max_n, u64 max_bytes) {
+    side_post(SIDE_PICK, hot, lim_rel, min_used, max_n, max_bytes, nullptr, 0);
+  }
+  void side_cold_scan(u32 window, u32 max_n) { side_post(SIDE_SCAN, window, 0, 0, max_n, 0, nullptr, 0); }
+  void side_cold_commit(py::buffer recs) { side_recs(SIDE_COMMIT, recs); }
+  void side_cold_in(py::buffer recs) { side_recs(SIDE_IN, recs); }
+  void side_cold_live() { side_post(SIDE_LIVE, 0, 0, 0, 0, 0, nullptr, 0); }
+  void side_recs(int kind, py::buffer recs) {
+    py::buffer_info bi = recs.request();
+    const size_t nb = (size_t)bi.size * bi.itemsize;
+    if (nb % sizeof(ColdRec) || nb / sizeof(ColdRec) > COLD_BATCH) throw std::runtime_error("cold: bad ColdRec batch");
+    side_post(kind, 0, 0, 0, 0, 0, (const ColdRec*)bi.ptr, (u32)(nb / sizeof(ColdRec)));
+  }
+  bool side_pending() {
+    std::lock_guard<std::mutex> g(side_mu_);
+    return side_.kind != SIDE_NONE;
+  }
+  bool side_queued() {
+    std::lock_guard<std::mutex> g(side_mu_);
+    return side_.kind && !side_.launched;
+  }
+  // launch(): the posted operation on stream s, ahead of the step's kernels
+  void run_side(hipStream_t s) {
+    std::lock_guard<std::mutex> g(side_mu_);
+    if (!side_.kind || side_.launched) return;
+    ColdRec* hrecs = (ColdRec*)((u8*)side_h_ + 64);
+    ColdRec* drecs = (ColdRec*)((u8*)side_d_ + 64);
+    switch (side_.kind) {
+      case SIDE_PICK:
+      case SIDE_SCAN:
+        HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s));
+        if (side_.kind == SIDE_PICK) {
+          HIPCHECK(hipMemsetAsync(cold_bytes_, 0, 8, s));
+          hipLaunchKernelGGL(k_cold_pick, dim3(d_.q_max), dim3(256), 0, s, par_[0].io, side_.a, side_.b, side_.c,
+                             cold_recs_, side_.max_n, cold_cnt_, cold_bytes_, side_.max_bytes);
+        } else {
+          HIPCHECK(hipMemsetAsync(cold_end_, 0, 8ull * d_.q_max, s));
+          hipLaunchKernelGGL(k_cold_scan, dim3(d_.q_max), dim3(64), 0, s, par_[0].io, side_.a, cold_recs_, side_.max_n,
+                             cold_cnt_, cold_end_);
+        }
+        hipLaunchKernelGGL(k_side_out, dim3(64), dim3(256), 0, s, (const ColdRec*)cold_recs_, (const u32*)cold_cnt_,
+                           side_.max_n, (u32*)drecs, (u32*)side_d_);
+        break;
+      case SIDE_COMMIT:
+      case SIDE_IN:
+        if (side_.n)
+          HIPCHECK(hipMemcpyAsync(cold_recs_, hrecs, sizeof(ColdRec) * side_.n, hipMemcpyHostToDevice, s));
+        if (side_.kind == SIDE_COMMIT) {
+          if (side_.n)
+            hipLaunchKernelGGL(k_cold_commit, blocks(side_.n, 256), dim3(256), 0, s, par_[0].io, cold_recs_, side_.n);
+        } else {
+          const u64 g2 = side_.n > d_.q_max ? side_.n : d_.q_max;
+          hipLaunchKernelGGL(k_cold_in, blocks(g2, 256), dim3(256), 0, s, par_[0].io, cold_recs_, side_.n, cold_end_);
+        }
+        break;
+      case SIDE_LIVE:
+        HIPCHECK(hipMemcpyAsync(side_live_h_, d_.cold_live, 8ull * COLD_SEGS, hipMemcpyDeviceToHost, s));
+        break;
     }
-    HIPCHECK(hipEventRecord(ev_done_[p], s_comp_));
-    gated_copy(slot_of_[p]);   // (phase B's last kernel opens the gate: sharded ranks gate too)
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(ev_side_, s));
+    side_.launched = true;
+    side_cv_.notify_all();
+  }
+  // the posted operation's result once it ran: ColdRec[] (pick / scan), cold_live bytes
+  // (live), b"" (commit / in); None while it has not finished within timeout_s
+  py::object side_wait(double timeout_s) {
+    int kind = SIDE_NONE;
+    hipError_t err = hipSuccess;
+    bool done = false;
+    {
+      py::gil_scoped_release nogil;   // (no Python objects in here)
+      std::unique_lock<std::mutex> g(side_mu_);
+      kind = side_.kind;
+      const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds((i64)(timeout_s * 1e6));
+      if (kind && side_cv_.wait_until(g, until, [&] { return side_.launched; })) {
+        g.unlock();
+        while (true) {
+          err = hipEventQuery(ev_side_);
+          if (err == hipSuccess) { done = true; break; }
+          if (err != hipErrorNotReady || std::chrono::steady_clock::now() > until) break;
+          std::this_thread::sleep_for(std::chrono::microseconds(50));
+        }
+      }
+    }
+    if (!kind) throw std::runtime_error("side_wait: nothing posted");
+    if (err != hipSuccess && err != hipErrorNotReady) HIPCHECK(err);
+    if (!done) return py::none();
+    std::lock_guard<std::mutex> g(side_mu_);
+    side_.kind = SIDE_NONE;
+    if (kind == SIDE_PICK || kind == SIDE_SCAN) {
+      const u32 n = *(volatile u32*)side_h_;
+      return py::bytes((const char*)side_h_ + 64, sizeof(ColdRec) * (size_t)n);
+    }
+    if (kind == SIDE_LIVE) return py::bytes((const char*)side_live_h_, 8ull * COLD_SEGS);
+    return py::bytes("");
+  }
+
+  // the operations that need the pipeline drained: no step in flight, no exchange pending
+  void between_steps(const char* what) {
+    if (any_inflight()) throw std::runtime_error(std::string(what) + "() between steps only");
+    for (int p = 0; native_x_ && p < npar_; ++p)
+      if (par_[p].counts_ready) throw std::runtime_error(std::string(what) + "() with an exchange pending");
+    sync();
+  }
+  py::bytes cold_fetch(u32 max_n) {
+    u32 n = 0;
+    HIPCHECK(hipMemcpyAsync(&n, cold_cnt_, 4, hipMemcpyDeviceToHost, s_comp_));
+    HIPCHECK(hipStreamSynchronize(s_comp_));
+    if (n > max_n) n = max_n;
+    std::string out(sizeof(ColdRec) * (size_t)n, '\0');
+    if (n) HIPCHECK(hipMemcpy(&out[0], cold_recs_, out.size(), hipMemcpyDeviceToHost));
+    return py::bytes(out);
+  }
+  u32 cold_upload(py::buffer recs) {
+    py::buffer_info bi = recs.request();
+    const size_t nb = (size_t)bi.size * bi.itemsize;
+    if (nb % sizeof(ColdRec) || nb / sizeof(ColdRec) > COLD_BATCH) throw std::runtime_error("cold: bad ColdRec batch");
+    const u32 n = (u32)(nb / sizeof(ColdRec));
+    if (n) HIPCHECK(hipMemcpy(cold_recs_, bi.ptr, nb, hipMemcpyHostToDevice));
+    return n;
+  }
+
+  // recovery: enqueue store records (RDesc with MF_RESTORE, payload [ex][rk][props][body])
+  // through the import path, between steps; returns the number of messages enqueued
+  u32 restore(py::buffer desc, py::buffer pay, i64 now_ms) {
+    py::buffer_info di = desc.request(), pi = pay.request();
+    u64 db = (u64)di.size * di.itemsize, pb = (u64)pi.size * pi.itemsize;
+    u32 n = (u32)(db / sizeof(RDesc));
+    // native exchange: restores run at a synchronisation point (no import pending) through
+    // parity 0's receive buffers
+    const RDesc* rdesc = d_.recv_desc ? d_.recv_desc : (native_x_ ? par_[0].io.recv_desc : nullptr);
+    const u8* rpay = d_.recv_pay ? d_.recv_pay : (native_x_ ? par_[0].io.recv_pay : nullptr);
+    if (!rdesc || n > d_.import_max || pb > d_.xfer_bytes)
+      throw std::runtime_error("restore batch exceeds the import buffers (restore_max / restore_bytes)");
+    between_steps("restore");
+    drain_egress();
+    if (db) HIPCHECK(hipMemcpy((void*)rdesc, di.ptr, db, hipMemcpyHostToDevice));
+    if (pb) HIPCHECK(hipMemcpy((void*)rpay, pi.ptr, pb, hipMemcpyHostToDevice));
+    DS& io = par_[0].io;
+    StepIn& in = *par_[0].stage_in;   // (k_stage copies it to the device; no step in flight)
+    in = StepIn{};
+    in.ref_back = 0xffffffffu;   // (no dispatch: nothing rendered)
+    in.nseg = 0;
+    in.now_ms = now_ms;
+    in.step = seq_;
+    in.id_ms = now_ms;
+    in.worker = 0;
+    in.egress = (u64)eg_[0].dev;
+    in.ingress = (u64)ing_[0].buf;
+    u32* x = par_[0].io.xchg_h;
+    for (u32 r = 0; r < 2 * WORLD_MAX; ++r) x[2 * WORLD_MAX + r] = x[XC_RECV_AN + r] = 0;
+    for (u32 r = 0; r < WORLD_MAX; ++r) x[XC_RACK_N + r] = 0;
+    x[2 * WORLD_MAX + d_.my_rank] = x[XC_RECV_AN + d_.my_rank] = n;
+    x[3 * WORLD_MAX + d_.my_rank] = x[XC_RECV_AB + d_.my_rank] = (u32)pb;
+    launch_ingest(s_comp_, io);
+    launch_route(s_comp_, io, d_.pub_max);
+    launch_phase_b(s_comp_, io, /*dispatch=*/false);
+    HIPCHECK(hipStreamSynchronize(s_comp_));
+    return par_[0].io.ctr_host_h->n_routed_msgs;
+  }
+
+  // Basic.Get between steps: (status, message_count, frames, tag, msg_id, qpos, persist,
+  // expired [(msg_id, q, qpos)] of durable x persistent messages dropped by the TTL skip)
+  py::tuple basic_get(u32 q, u32 chslot, u32 noack, i64 now_ms) {
+    if (any_inflight()) throw std::runtime_error("basic_get() between steps only");
+    if (q >= d_.q_max || chslot >= d_.c_max * d_.chpc) throw std::runtime_error("basic_get: bad queue / channel");
+    Range rg("chanamq.basic_get");
+    sync();
+    hipLaunchKernelGGL(k_basic_get, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms, get_out_dev_,
+                       get_cap_, get_res_dev_);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s_comp_));
+    const GetRes& r = *get_res_h_;
+    py::list exp;
+    for (u32 i = 0; i < r.n_exp && i < GET_EXP_MAX; ++i)
+      exp.append(py::make_tuple(r.exp[i].msg_id, r.exp[i].q, r.exp[i].qpos));
+    py::bytes frames(r.status == GET_OK ? (const char*)get_out_h_ : "", r.status == GET_OK ? r.out_len : 0);
+    return py::make_tuple(r.status, r.msg_count, frames, r.tag, r.msg_id, r.qpos, r.persist, exp);
   }
 
   // ------------------------------------------------------------- native front end
@@ -2197,31 +2563,25 @@ class Engine {
       return ((Engine*)e)->guard([&] { ((Engine*)e)->egress_wait_slot(slot); return 0; });
     };
     a.error = [](void* e) -> const char* { return ((Engine*)e)->err_.c_str(); };
-    a.counters = [](void* e, int p) -> const Counters* { return ((Engine*)e)->io_[p].ctr_host_h; };
-    a.seg_out = [](void* e, int p) -> const SegOut* { return ((Engine*)e)->io_[p].seg_out_hh; };
-    a.conn_out = [](void* e, int p) -> const ConnOut* { return ((Engine*)e)->io_[p].conn_out_hh; };
-    a.ctrl_rec = [](void* e, int p) -> const CtrlRec* { return ((Engine*)e)->io_[p].ctrl_rec_hh; };
-    a.ctrl = [](void* e, int p) -> const u8* { return ((Engine*)e)->io_[p].ctrl_hh; };
-    a.egress_host = [](void* e, int slot) -> const u8* { return ((Engine*)e)->egress_host_[slot]; };
+    a.counters = [](void* e, int p) -> const Counters* { return ((Engine*)e)->par_[p].io.ctr_host_h; };
+    a.seg_out = [](void* e, int p) -> const SegOut* { return ((Engine*)e)->par_[p].io.seg_out_hh; };
+    a.conn_out = [](void* e, int p) -> const ConnOut* { return ((Engine*)e)->par_[p].io.conn_out_hh; };
+    a.ctrl_rec = [](void* e, int p) -> const CtrlRec* { return ((Engine*)e)->par_[p].io.ctrl_rec_hh; };
+    a.ctrl = [](void* e, int p) -> const u8* { return ((Engine*)e)->par_[p].io.ctrl_hh; };
+    a.egress_host = [](void* e, int slot) -> const u8* { return ((Engine*)e)->eg_[slot].host; };
     a.persist_host = [](void* e, int p) -> const u8* { return ((Engine*)e)->pslot_host(p); };
     a.consumed_host = [](void* e, int p) -> const ConsumedRec* { return ((Engine*)e)->cslot_host(p); };
-    a.wblock = (u32*)buf("conn_wblock").ptr;
-    a.grow_host = [](void* e, int p) -> const RingMove* { return ((Engine*)e)->io_[p].grow_hh; };
-    a.conn_conf = [](void* e, int p) -> const u32* { return ((Engine*)e)->io_[p].conn_conf_hh; };
+    a.wblock = wblock_h_;
+    a.grow_host = [](void* e, int p) -> const RingMove* { return ((Engine*)e)->par_[p].io.grow_hh; };
+    a.conn_conf = [](void* e, int p) -> const u32* { return ((Engine*)e)->par_[p].io.conn_conf_hh; };
     a.world = d_.world;
     a.rank = d_.my_rank;
     a.native_xchg = native_x_ ? 1u : 0u;
-    a.exchange = [](void* e, int q, u32 flags, u32* orf) -> int {
-      Engine* E = (Engine*)e;
-      int rc = 0;
-      int g = E->guard([&] { rc = E->exchange(q, flags, orf); return 0; });
-      return g < 0 ? -1 : rc;
+    a.exchange = [](void* e, int q, u32 flags, u32* orf) -> int {   // (0 / -2; -1: threw)
+      return ((Engine*)e)->guard([&] { return ((Engine*)e)->exchange(q, flags, orf); });
     };
     a.drop_exchange = [](void* e, int q) -> int {
-      Engine* E = (Engine*)e;
-      int rc = 0;
-      int g = E->guard([&] { rc = E->drop_exchange(q); return 0; });
-      return g < 0 ? -1 : rc;
+      return ((Engine*)e)->guard([&] { return ((Engine*)e)->drop_exchange(q); });
     };
     a.launch_b = [](void* e, int p) -> int {
       return ((Engine*)e)->guard([&] { ((Engine*)e)->launch_b(p); return 0; });
@@ -2244,30 +2604,18 @@ class Engine {
     a.stage_gets = [](void* e, const GetReq* r, u32 n) -> int {
       return ((Engine*)e)->guard([&] { ((Engine*)e)->stage_gets(r, n); return 0; });
     };
-    a.get_out = [](void* e, int p) -> const GetOut* { return ((Engine*)e)->io_[p].get_out_hh; };
+    a.get_out = [](void* e, int p) -> const GetOut* { return ((Engine*)e)->par_[p].io.get_out_hh; };
     a.host_work = [](void* e) -> int { return ((Engine*)e)->host_work() ? 1 : 0; };
     a.dl_state = [](void* e, int which) -> u64 { return ((Engine*)e)->dl_state(which); };
     a.unpaused = [](void* e, int p, const u32** out) -> u32 {
       Engine* en = (Engine*)e;
-      if (p < 0 || p > 1) return 0;
-      *out = en->stage_unp_[p];
-      return en->nunp_[p];
+      if (p < 0 || p >= en->npar_) return 0;
+      *out = en->par_[p].stage_unp;
+      return en->par_[p].nunp;
     };
     a.set_egress_ref = [](void* e, int back, u32 min_bytes) -> int {
       return ((Engine*)e)->guard([&] { ((Engine*)e)->set_egress_ref(back, min_bytes); return 0; });
     };
-    for (int p = 0; p < npar_; ++p) {
-      std::string sfx = std::to_string(p);
-      HostIO& h = io_[p];
-      h.ctr_host_h = (const Counters*)buf("ctr_host" + sfx).ptr;
-      h.seg_out_hh = (const SegOut*)buf("seg_out" + sfx).ptr;
-      h.conn_out_hh = (const ConnOut*)buf("conn_out" + sfx).ptr;
-      h.ctrl_rec_hh = (const CtrlRec*)buf("ctrl_rec" + sfx).ptr;
-      h.ctrl_hh = (const u8*)buf("ctrl" + sfx).ptr;
-      h.grow_hh = (const RingMove*)buf("grow" + sfx).ptr;
-      h.conn_conf_hh = (const u32*)buf("conn_conf" + sfx).ptr;
-      h.get_out_hh = (const GetOut*)buf("get_out" + sfx).ptr;
-    }
     return (u64)&api_;
   }
 
@@ -2280,341 +2628,6 @@ class Engine {
       err_ = ex.what();
       return -1;
     }
-  }
-
-  // egress_wait_slot without touching engine state (any thread; the slot's D2H was
-  // issued before the caller learnt of the slot)
-  void egress_ready(int e) {
-    if (copy_mode_ == 3) {
-      if (sdma_pending_[e]) bounded_wait(sdma_sig_[e], e, "egress D2H");
-      if (tail_pending_[e]) bounded_wait(tail_sig_[e], e, "egress tail D2H");
-      return;
-    }
-    if (d2h_issued_[e]) HIPCHECK(hipEventSynchronize(ev_d2h_[e]));
-  }
-
-  void egress_wait_slot(int e) {
-    HostTimer ht(&ht_[5]);
-    if (copy_mode_ == 3) { sdma_wait(e); return; }
-    if (d2h_issued_[e]) HIPCHECK(hipEventSynchronize(ev_d2h_[e]));
-  }
-
-  // the egress D2H of slot e, queued now: starts when the step's last kernel opens the gate
-  void gated_copy(int e) {
-    if (!spec_[e]) return;
-    Range rg("chanamq.K5.egress_gated");
-    // sdma_split 2: the speculative copy in two halves on two SDMA engines, both released by
-    // the same gate, each decrementing the slot's completion signal once
-    const u64 n = spec_[e];
-    const int k = (sdma_split_ > 1 && sdma_engine2_ && n >= (4u << 20)) ? 2 : 1;
-    const u64 half = k == 2 ? ((n / 2) & ~(u64)4095) : n;
-    hsa_signal_store_screlease(sdma_sig_[e], k);
-    for (int i = 0; i < k; ++i) {
-      const u64 off = i ? half : 0, len = i ? n - half : half;
-      hsa_status_t st = hsa_amd_memory_async_copy_on_engine((u8*)egress_host_[e] + off, cpu_agent_,
-                                                            (u8*)egress_dev_[e] + off, gpu_agent_, len, 1,
-                                                            &gate_sig_[e], sdma_sig_[e],
-                                                            i ? sdma_engine2_ : sdma_engine_, true);
-      if (st != HSA_STATUS_SUCCESS) {
-        hsa_signal_store_screlease(sdma_sig_[e], 0);
-        throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (gated egress) failed");
-      }
-    }
-    sdma_pending_[e] = true;
-    ++eg_stats_[0];
-    eg_stats_[2] += spec_[e];
-  }
-
-  // non-blocking: the launched step of parity p has finished (its results are readable)
-  bool step_done(int p) {
-    if (!inflight_[p] || staged_[p] || phase_a_[p] || b_due_[p]) return !inflight_[p];
-    return hipEventQuery(ev_done_[p]) == hipSuccess;
-  }
-  // non-blocking: egress slot e's D2H (and tail) landed in host memory
-  bool egress_done_slot(int e) {
-    if (copy_mode_ == 3) {
-      if (sdma_pending_[e] && hsa_signal_load_scacquire(sdma_sig_[e]) != 0) return false;
-      if (tail_pending_[e] && hsa_signal_load_scacquire(tail_sig_[e]) != 0) return false;
-      sdma_pending_[e] = tail_pending_[e] = false;
-      return true;
-    }
-    return !d2h_issued_[e] || hipEventQuery(ev_d2h_[e]) == hipSuccess;
-  }
-
-  void wait_results(int p) {
-    HostTimer ht(&ht_[3]);
-    Range rg("chanamq.step.wait_results");
-    if (phase_a_[p] || b_due_[p]) throw std::runtime_error("wait_results: phase B of this sharded step not submitted");
-    if (staged_[p]) throw std::runtime_error("wait_results: step staged but never launched");
-    HIPCHECK(hipEventSynchronize(ev_done_[p]));
-    inflight_[p] = false;
-    if (h2d_addr_[p]) {   // (k_h2d_wait gives up after its poll budget: the step then ran on a stale slot)
-      if (*(volatile const i64*)h2d_addr_[p] != 0 || (h2d_addr2_[p] && *(volatile const i64*)h2d_addr2_[p] != 0)) {
-        wait_failed_ = true;
-        throw std::runtime_error("ingress copy of step " + std::to_string(launch_seq_[p]) +
-                                 " did not complete before its step ran (HSA SDMA copy lost)");
-      }
-    }
-    // egress history of the gated copies' sizing (every finished step, idle ones too)
-    const u64 n = ((const Counters*)buf("ctr_host" + std::to_string(p)).ptr)->egress_bytes;
-    eg_hist_[eg_hist_i_++ & 3] = n;
-    eg_stats_[3] += n;
-  }
-
-  u64 egress_copy(int p) {
-    HostTimer ht(&ht_[4]);
-    Range rg("chanamq.K5.egress_d2h");
-    const Counters* c = (const Counters*)buf("ctr_host" + std::to_string(p)).ptr;
-    u64 n = c->egress_bytes;
-    const int e = slot_of_[p];
-    if (spec_[e]) {   // gated: the bulk is on its way already; the host only adds a tail
-      if (n > spec_[e]) {
-        const u64 off = spec_[e];
-        hsa_signal_store_screlease(tail_sig_[e], 1);
-        hsa_status_t st = hsa_amd_memory_async_copy_on_engine((u8*)egress_host_[e] + off, cpu_agent_,
-                                                              (u8*)egress_dev_[e] + off, gpu_agent_, n - off, 0, nullptr,
-                                                              tail_sig_[e], tail_engine_, true);
-        if (st != HSA_STATUS_SUCCESS) {
-          hsa_signal_store_screlease(tail_sig_[e], 0);
-          throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (egress tail) failed");
-        }
-        tail_pending_[e] = true;
-        ++eg_stats_[1];
-      }
-      return n;
-    }
-    if (eager_d2h_[p]) {   // already queued behind the step (launch)
-      eager_d2h_[p] = false;
-      return n;
-    }
-    HIPCHECK(hipStreamWaitEvent(s_d2h_, ev_done_[p], 0));
-    if (n && copy_mode_ == 3) {
-      HIPCHECK(hipEventSynchronize(ev_done_[p]));
-      // sdma_split 2: large egress split over two SDMA engines, each part decrementing the
-      // slot's signal once (measured slower on MI355X: 28.9 vs 38.6 M msgs/s, p99 6.6 ms,
-      // profiles/r4_sdma_split.md -- off by default)
-      const int k = (n >= (2u << 20) && sdma_engine2_) ? 2 : 1;
-      hsa_signal_store_screlease(sdma_sig_[e], k);
-      const u64 half = k == 2 ? ((n / 2) & ~(u64)4095) : n;
-      for (int i = 0; i < k; ++i) {
-        const u64 off = i ? half : 0, len = i ? n - half : half;
-        hsa_status_t st = hsa_amd_memory_async_copy_on_engine(
-            (u8*)egress_host_[e] + off, cpu_agent_, (u8*)egress_dev_[e] + off, gpu_agent_, len, 0, nullptr,
-            sdma_sig_[e], i ? sdma_engine2_ : sdma_engine_, true);
-        if (st != HSA_STATUS_SUCCESS) throw std::runtime_error("hsa_amd_memory_async_copy_on_engine failed");
-      }
-      sdma_pending_[e] = true;
-      return n;
-    }
-    if (n && copy_mode_ == 2)
-      hipLaunchKernelGGL(k_copy_out, dim3(copy_wgs_), dim3(256), 0, s_d2h_, egress_host_dev_[e],
-                         (const u8*)egress_dev_[e], n);
-    else if (n)
-      HIPCHECK(hipMemcpyAsync(egress_host_[e], egress_dev_[e], n,
-                              sdma_ ? hipMemcpyDeviceToDeviceNoCU : hipMemcpyDeviceToHost, s_d2h_));
-    HIPCHECK(hipEventRecord(ev_d2h_[e], s_d2h_));
-    d2h_issued_[e] = true;
-    return n;
-  }
-
-  void egress_wait(int p) {
-    HostTimer ht(&ht_[5]);
-    const int e = slot_of_[p];
-    if (copy_mode_ == 3) { sdma_wait(e); return; }
-    HIPCHECK(hipEventSynchronize(ev_d2h_[e]));
-  }
-
-  // the slot's D2H (+ its tail) complete
-  void sdma_wait(int e) {
-    if (sdma_pending_[e]) bounded_wait(sdma_sig_[e], e, "egress D2H");
-    if (tail_pending_[e]) bounded_wait(tail_sig_[e], e, "egress tail D2H");
-    sdma_pending_[e] = false;
-    tail_pending_[e] = false;
-  }
-
-  // a copy's completion signal reaching 0: an active spin first (a step's egress lands
-  // within its period; a blocked wait would add the interrupt wake-up to every delivery's
-  // latency), then blocked waits up to the engine's wait deadline -- past it the copy is
-  // declared lost: the slot's gate is opened (a gated copy that never saw its step's last
-  // kernel would otherwise hold its SDMA queue forever) and the engine reports an error
-  // (the front end's healthy() turns false, a sharded node fails over).  Was: an unbounded
-  // active wait, a core spinning forever on a lost gate (VERDICT r5 weak 6)
-  void bounded_wait(hsa_signal_t sig, int e, const char* what) {
-    if (hsa_signal_wait_scacquire(sig, HSA_SIGNAL_CONDITION_EQ, 0, spin_ticks_, HSA_WAIT_STATE_ACTIVE) == 0) return;
-    const auto t0 = std::chrono::steady_clock::now();
-    while (hsa_signal_wait_scacquire(sig, HSA_SIGNAL_CONDITION_EQ, 0, block_ticks_, HSA_WAIT_STATE_BLOCKED) != 0) {
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(wait_ms_)) {
-        if (e >= 0 && gate_sig_[e].handle) hsa_signal_store_screlease(gate_sig_[e], 0);
-        wait_failed_ = true;
-        throw std::runtime_error(std::string(what) + " of egress slot " + std::to_string(e) + " did not complete within " +
-                                 std::to_string(wait_ms_) + " ms (gate never opened / copy lost)");
-      }
-    }
-  }
-  // fault injection (tests): the next submitted step's egress gate is never opened by its
-  // last kernel (it stores to a scratch word instead), as after a step that died before it
-  void inject_gate_fault() { gate_fault_ = true; }
-  // (tests) the next step's ingress wait polls a word that never reaches 0 (HSA ingress only)
-  void inject_h2d_fault() { h2d_fault_ = true; }
-  bool wait_failed() const { return wait_failed_; }
-
-  // gated egress: bytes to copy speculatively for the next step -- the largest of the last
-  // four steps' egress + 1/16 + 64 KB, in 64 KB units (0 after four steps without egress)
-  u64 spec_bytes() const {
-    u64 mx = 0;
-    for (u64 v : eg_hist_) mx = v > mx ? v : mx;
-    if (!mx) return 0;
-    const u64 sz = (mx + mx / 16 + (64u << 10) + 65535) & ~(u64)65535;
-    return sz < egress_alloc_ ? sz : egress_alloc_;
-  }
-  // gated egress counters: [gated copies, tail copies, bytes copied speculatively, bytes rendered]
-  py::dict egress_stats() const {
-    py::dict o;
-    o["gated"] = gated_;
-    o["gated_copies"] = eg_stats_[0];
-    o["tail_copies"] = eg_stats_[1];
-    o["spec_bytes"] = eg_stats_[2];
-    o["egress_bytes"] = eg_stats_[3];
-    return o;
-  }
-
-  // egress slot (host view "egress_host<slot>") of the step last submitted with parity p
-  int egress_slot(int p) const { return slot_of_[p]; }
-  // egress by reference from the next submitted step on (StepIn.ref_back): bodies of the
-  // last `back` steps' ingress payloads (-1: off; -2: only bodies in the host spill ring) of
-  // at least min_bytes are not rendered;
-  // the caller keeps those payloads unchanged until the delivering step's egress is sent
-  void set_egress_ref(int back, u32 min_bytes) {
-    if (back > 64) throw std::runtime_error("set_egress_ref: at most 64 steps back");
-    ref_back_ = back == -2 ? -2 : back < 0 ? -1 : back;
-    ref_min_ = min_bytes < 16 ? 16 : min_bytes;
-  }
-  // store-record slot (host views "persist<slot>" / "consumed<slot>") of that step
-  int persist_slot(int p) const { return pslot_of_[p]; }
-  const u8* pslot_host(int p) {
-    return d_.persist ? (const u8*)buf("persist" + std::to_string(pslot_of_[p])).ptr : nullptr;
-  }
-  const ConsumedRec* cslot_host(int p) {
-    return d_.persist ? (const ConsumedRec*)buf("consumed" + std::to_string(pslot_of_[p])).ptr : nullptr;
-  }
-
-  // HSA agents of this device and of the host, an SDMA engine for GPU -> host copies
-  void init_sdma() {
-    if (hsa_init() != HSA_STATUS_SUCCESS) throw std::runtime_error("hsa_init failed");
-    struct Ctx { std::vector<hsa_agent_t> gpus, cpus; } ctx;
-    hsa_iterate_agents([](hsa_agent_t a, void* data) {
-      hsa_device_type_t t;
-      hsa_agent_get_info(a, HSA_AGENT_INFO_DEVICE, &t);
-      auto* c = (Ctx*)data;
-      if (t == HSA_DEVICE_TYPE_GPU) c->gpus.push_back(a);
-      else if (t == HSA_DEVICE_TYPE_CPU) c->cpus.push_back(a);
-      return HSA_STATUS_SUCCESS;
-    }, &ctx);
-    if ((int)ctx.gpus.size() <= device_ || ctx.cpus.empty()) throw std::runtime_error("HSA agents not found");
-    {   // bounded_wait: spin 2 ms actively, then block in 1 ms slices
-      u64 f = 0;
-      if (hsa_system_get_info(HSA_SYSTEM_INFO_TIMESTAMP_FREQUENCY, &f) != HSA_STATUS_SUCCESS || !f) f = 100000000ull;
-      spin_ticks_ = f / 500;
-      block_ticks_ = f / 1000;
-    }
-    gpu_agent_ = ctx.gpus[device_];
-    cpu_agent_ = ctx.cpus[0];
-    uint32_t mask = 0;
-    if (hsa_amd_memory_copy_engine_status(cpu_agent_, gpu_agent_, &mask) != HSA_STATUS_SUCCESS || !mask)
-      throw std::runtime_error("no SDMA engine available for device -> host copies");
-    // not the engine of the runtime's own H2D copies: one SDMA engine serialises both
-    // directions (measured 54 GB/s total vs 94 GB/s on two engines, bench/pcie_probe.hip)
-    // (measured on MI355X: engines 0-3 reach PCIe rate, 8 and 15 a third of it)
-    u32 pick = 0;
-    if (sdma_pref_ >= 0 && (mask >> sdma_pref_) & 1u) pick = (u32)sdma_pref_;
-    else if ((mask >> 1) & 1u) pick = 1;
-    else while (!((mask >> pick) & 1u)) ++pick;
-    sdma_engine_ = (hsa_amd_sdma_engine_id_t)(1u << pick);
-    // a second engine for split egress copies: another full-rate one (0-3), not engine 0
-    // (the runtime's H2D engine) when there is a choice
-    sdma_engine2_ = (hsa_amd_sdma_engine_id_t)0;
-    if (sdma_split_ > 1)
-      for (u32 c : {2u, 3u, 0u})
-        if (c != pick && ((mask >> c) & 1u)) { sdma_engine2_ = (hsa_amd_sdma_engine_id_t)(1u << c); break; }
-    // the tail engine (gated egress): another full-rate engine than the gated copies' --
-    // which can sit behind the next step's gate -- and than the runtime's H2D engine 0
-    // (nor the split copies' second engine: an engine's queue is in order, and a gated copy
-    // waiting there for the next step's gate would hold the tail back by a step)
-    tail_engine_ = sdma_engine_;
-    for (u32 c : {2u, 3u, 0u})
-      if (c != pick && ((mask >> c) & 1u) && (1u << c) != (u32)sdma_engine2_) {
-        tail_engine_ = (hsa_amd_sdma_engine_id_t)(1u << c);
-        break;
-      }
-    // the ingress engine (cfg h2d_hsa): engine 0, the runtime's own H2D engine -- the egress
-    // engines stay free of it (measured: egress on engine 0 next to the ingress copies halves
-    // the throughput, profiles/r6_x); else any full-rate engine the egress does not use
-    ing_engine_ = (hsa_amd_sdma_engine_id_t)0;
-    for (u32 c : {0u, 3u, 2u, 1u})
-      if (((mask >> c) & 1u) && (1u << c) != (u32)sdma_engine_ && (1u << c) != (u32)sdma_engine2_ &&
-          (1u << c) != (u32)tail_engine_) {
-        ing_engine_ = (hsa_amd_sdma_engine_id_t)(1u << c);
-        break;
-      }
-    if (!ing_engine_) ing_engine_ = tail_engine_;
-    // a split payload's second engine (cfg h2d_split, default off): another full-rate one the
-    // egress does not use
-    ing_engine2_ = (hsa_amd_sdma_engine_id_t)0;
-    if (h2d_split_cfg_)
-      for (u32 c : {3u, 2u})
-        if (((mask >> c) & 1u) && (1u << c) != (u32)ing_engine_ && (1u << c) != (u32)sdma_engine_ &&
-            (1u << c) != (u32)sdma_engine2_ && (1u << c) != (u32)tail_engine_) {
-          ing_engine2_ = (hsa_amd_sdma_engine_id_t)(1u << c);
-          break;
-        }
-    for (int e = 0; e < EGRESS_SLOTS; ++e)
-      if (hsa_signal_create(0, 0, nullptr, &sdma_sig_[e]) != HSA_STATUS_SUCCESS ||
-          hsa_signal_create(0, 0, nullptr, &tail_sig_[e]) != HSA_STATUS_SUCCESS ||
-          hsa_signal_create(0, 0, nullptr, &gate_sig_[e]) != HSA_STATUS_SUCCESS)
-        throw std::runtime_error("hsa_signal_create failed");
-  }
-
-  void drain_egress() {
-    for (int e = 0; e < EGRESS_SLOTS; ++e) {
-      sdma_wait(e);
-      if (d2h_issued_[e]) HIPCHECK(hipEventSynchronize(ev_d2h_[e]));
-    }
-  }
-
-  void sync() {
-    HIPCHECK(hipStreamSynchronize(s_h2d_));
-    if (s_h2d_alt_) HIPCHECK(hipStreamSynchronize(s_h2d_alt_));
-    HIPCHECK(hipStreamSynchronize(s_pre_));
-    HIPCHECK(hipStreamSynchronize(s_ing_));
-    HIPCHECK(hipStreamSynchronize(s_comp_));
-    HIPCHECK(hipStreamSynchronize(s_d2h_));
-  }
-
-  // seconds spent in each host phase since the last reset
-  py::dict host_times(bool reset) {
-    // (asynchronous exchange: "exchange" is the stepper's wait for the previous job,
-    // "exchange_thread" and "exchange_counts" the exchange thread's time)
-    static const char* names[9] = {"submit", "submit_sdma_wait", "submit_graph_launch", "wait_results",
-                                   "egress_copy", "egress_wait", "exchange", "exchange_counts", "exchange_thread"};
-    py::dict o;
-    for (int i = 0; i < 9; ++i) { o[names[i]] = ht_[i]; if (reset) ht_[i] = 0; }
-    return o;
-  }
-
-  py::dict counters(int p) const {
-    const Counters& c = *(const Counters*)buf("ctr_host" + std::to_string(p)).ptr;
-    py::dict o;
-#define F(x) o[#x] = c.x
-    F(n_cmds); F(n_frags); F(n_pubs); F(n_acks); F(n_ctrl); F(ctrl_bytes); F(n_pairs); F(n_deliv);
-    F(egress_bytes); F(n_returns); F(n_confirm_frames); F(n_freed); F(n_requeue); F(n_unroutable);
-    F(n_dropped_nomem); F(n_expired); F(n_routed_msgs); F(n_unknown_exchange); F(n_ring_full);
-    F(n_acked); F(log_head); F(log_tail); F(msg_free_top); F(n_live_msgs);
-    F(n_persist); F(n_consumed); F(persist_used); F(n_persist_overflow);
-    F(live_bytes); F(n_grow); F(n_dget); F(spill_moved); F(n_ref); F(gath_off); F(ref_bytes);
-#undef F
-    std::vector<u32> lat(c.lat_hist, c.lat_hist + LAT_BINS);
-    o["lat_hist"] = lat;
-    return o;
   }
 
  private:
@@ -2638,41 +2651,34 @@ class Engine {
     hipLaunchKernelGGL((k_scan<4, 4>), dim3(nb), dim3(1024), 0, s, a, d.tot, ingest ? scan_status_ing_ : scan_status_,
                        ingest ? scan_ctl_ing_ : scan_ctl_, scan_smax_);
   }
+  // f(std::integral_constant<u32, B>{}) for the digit width B of a sort pass over `bits` key
+  // bits: 8 (or fewer) .. 11, the widths the sort kernels are instantiated for
+  template <class F>
+  static void with_key_bits(u32 bits, F&& f) {
+    if (bits <= 8) f(std::integral_constant<u32, 8>{});
+    else if (bits == 9) f(std::integral_constant<u32, 9>{});
+    else if (bits == 10) f(std::integral_constant<u32, 10>{});
+    else f(std::integral_constant<u32, 11>{});
+  }
   // returns index (0/1) of the buffer holding the sorted output
   u32 radix_sort(hipStream_t s, const DS& d, u32** keys, u32** vals, const u32* n, u32 nmax, u32 bits) {
-    u32 ntiles = ceil_div(nmax, SORT_TILE);
-    if (bits > 8 && bits <= 11) {   // one 9..11-bit pass instead of two 8-bit ones
-      if (bits == 9) {
-        hipLaunchKernelGGL(k_rs_hist<9>, capped(ntiles, 256), dim3(RsNt<9>::v), 0, s, keys[0], n, 0u, d_.hist,
-                           d_.hist_scan, &d.tot[TS_RS_TICKET], ntiles);
-        hipLaunchKernelGGL(k_rs_scatter<9>, capped(ntiles, 256), dim3(256), 0, s, keys[0], vals[0], keys[1], vals[1], n,
-                           0u, d_.hist_scan, ntiles);
-      } else if (bits == 10) {
-        hipLaunchKernelGGL(k_rs_hist<10>, capped(ntiles, 256), dim3(RsNt<10>::v), 0, s, keys[0], n, 0u, d_.hist,
-                           d_.hist_scan, &d.tot[TS_RS_TICKET], ntiles);
-        hipLaunchKernelGGL(k_rs_scatter<10>, capped(ntiles, 256), dim3(256), 0, s, keys[0], vals[0], keys[1], vals[1],
-                           n, 0u, d_.hist_scan, ntiles);
-      } else {
-        hipLaunchKernelGGL(k_rs_hist<11>, capped(ntiles, 256), dim3(RsNt<11>::v), 0, s, keys[0], n, 0u, d_.hist,
-                           d_.hist_scan, &d.tot[TS_RS_TICKET], ntiles);
-        hipLaunchKernelGGL(k_rs_scatter<11>, capped(ntiles, 256), dim3(256), 0, s, keys[0], vals[0], keys[1], vals[1],
-                           n, 0u, d_.hist_scan, ntiles);
-      }
-      return 1;
-    }
+    const u32 ntiles = ceil_div(nmax, SORT_TILE);
+    const u32 digit = bits > 8 && bits <= 11 ? bits : 8;   // one 9..11-bit pass instead of two 8-bit ones
     u32 src = 0;
-    for (u32 shift = 0; shift < bits; shift += 8) {
-      hipLaunchKernelGGL(k_rs_hist<8>, capped(ntiles, 256), dim3(RsNt<8>::v), 0, s, keys[src], n, shift, d_.hist, d_.hist_scan,
-                         &d.tot[TS_RS_TICKET], ntiles);
-      hipLaunchKernelGGL(k_rs_scatter<8>, capped(ntiles, 256), dim3(256), 0, s, keys[src], vals[src], keys[src ^ 1],
-                         vals[src ^ 1], n, shift, d_.hist_scan, ntiles);
+    for (u32 shift = 0; shift < bits; shift += digit) {
+      with_key_bits(digit, [&](auto b) {
+        constexpr u32 B = decltype(b)::value;
+        hipLaunchKernelGGL(k_rs_hist<B>, capped(ntiles, 256), dim3(RsNt<B>::v), 0, s, keys[src], n, shift, d_.hist,
+                           d_.hist_scan, &d.tot[TS_RS_TICKET], ntiles);
+        hipLaunchKernelGGL(k_rs_scatter<B>, capped(ntiles, 256), dim3(256), 0, s, keys[src], vals[src], keys[src ^ 1],
+                           vals[src ^ 1], n, shift, d_.hist_scan, ntiles);
+      });
       src ^= 1;
     }
     return src;
   }
 
   static dim3 blocks(u64 n, u32 per) { return dim3(n ? ceil_div(n, per) : 1); }
-  // wave-per-item grid-stride kernels: 4 waves per block, at most 8192 blocks
   // wave-per-item grid-stride kernels: 4 waves per block, at most 8192 blocks.  Grids are
   // fixed at graph capture, sized for capacity; the cap keeps a step with a fraction of
   // the capacity from launching (and retiring) 100K+ idle waves, while still giving the
@@ -2737,19 +2743,11 @@ class Engine {
       const u32 nt = ceil_div(d.pair_max, SORT_TILE);
       const u32* n = &d.tot[TS_PAIR_N];
       u32* tk = &d.tot[TS_RS_TICKET];
-      if (pbits <= 8) {
-        hipLaunchKernelGGL(k_rs_hist_plan<8>, capped(nt, 256), dim3(RsNt<8>::v), 0, s, d, d.pair_k[0], n, d_.hist, d_.hist_scan, tk, nt);
-        hipLaunchKernelGGL(k_rs_scatter_enq<8>, capped(nt, 256), dim3(256), 0, s, d, d.pair_k[0], d.pair_v[0], n, d_.hist_scan);
-      } else if (pbits == 9) {
-        hipLaunchKernelGGL(k_rs_hist_plan<9>, capped(nt, 256), dim3(RsNt<9>::v), 0, s, d, d.pair_k[0], n, d_.hist, d_.hist_scan, tk, nt);
-        hipLaunchKernelGGL(k_rs_scatter_enq<9>, capped(nt, 256), dim3(256), 0, s, d, d.pair_k[0], d.pair_v[0], n, d_.hist_scan);
-      } else if (pbits == 10) {
-        hipLaunchKernelGGL(k_rs_hist_plan<10>, capped(nt, 256), dim3(RsNt<10>::v), 0, s, d, d.pair_k[0], n, d_.hist, d_.hist_scan, tk, nt);
-        hipLaunchKernelGGL(k_rs_scatter_enq<10>, capped(nt, 256), dim3(256), 0, s, d, d.pair_k[0], d.pair_v[0], n, d_.hist_scan);
-      } else {
-        hipLaunchKernelGGL(k_rs_hist_plan<11>, capped(nt, 256), dim3(RsNt<11>::v), 0, s, d, d.pair_k[0], n, d_.hist, d_.hist_scan, tk, nt);
-        hipLaunchKernelGGL(k_rs_scatter_enq<11>, capped(nt, 256), dim3(256), 0, s, d, d.pair_k[0], d.pair_v[0], n, d_.hist_scan);
-      }
+      with_key_bits(pbits, [&](auto b) {
+        constexpr u32 B = decltype(b)::value;
+        hipLaunchKernelGGL(k_rs_hist_plan<B>, capped(nt, 256), dim3(RsNt<B>::v), 0, s, d, d.pair_k[0], n, d_.hist, d_.hist_scan, tk, nt);
+        hipLaunchKernelGGL(k_rs_scatter_enq<B>, capped(nt, 256), dim3(256), 0, s, d, d.pair_k[0], d.pair_v[0], n, d_.hist_scan);
+      });
     } else {
       u32* pk[2] = {d.pair_k[0], d.pair_k[1]};
       u32* pv[2] = {d.pair_v[0], d.pair_v[1]};
@@ -2810,7 +2808,8 @@ class Engine {
     launch_route(s, d, d.pub_max);
     launch_tail(s, d);
   }
-  void capture_on(hipStream_t st, hipGraphExec_t* ge, const std::function<void()>& f) {
+  // the launches f makes on stream st, captured once into *ge
+  void capture(hipStream_t st, hipGraphExec_t* ge, const std::function<void()>& f) {
     hipGraph_t g;
     std::lock_guard<std::mutex> cg(cap_mu_);   // (no exchange-thread HIP call inside a capture)
     HIPCHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -2826,275 +2825,6 @@ class Engine {
     launch_route(s, d, d.import_max, /*imports=*/true);
     launch_tail(s, d, dispatch);
   }
-
-  void capture_main(int p) {
-    hipGraph_t g;
-    std::lock_guard<std::mutex> cg(cap_mu_);   // (no exchange-thread HIP call inside a capture)
-    HIPCHECK(hipStreamBeginCapture(s_comp_, hipStreamCaptureModeThreadLocal));
-    launch_main(s_comp_, io_[p]);
-    HIPCHECK(hipStreamEndCapture(s_comp_, &g));
-    HIPCHECK(hipGraphInstantiate(&graph_exec_[p], g, nullptr, nullptr, 0));
-    HIPCHECK(hipGraphDestroy(g));
-  }
-
-  void capture_b(int p) {
-    hipGraph_t g;
-    std::lock_guard<std::mutex> cg(cap_mu_);   // (no exchange-thread HIP call inside a capture)
-    HIPCHECK(hipStreamBeginCapture(s_comp_, hipStreamCaptureModeThreadLocal));
-    launch_phase_b(s_comp_, io_[p]);
-    HIPCHECK(hipStreamEndCapture(s_comp_, &g));
-    HIPCHECK(hipGraphInstantiate(&graph_b_[p], g, nullptr, nullptr, 0));
-    HIPCHECK(hipGraphDestroy(g));
-  }
-
-  int device_ = 0;
-  u32 n_cu_ = 256;   // compute units of the device (grid caps of the block-per-segment / group kernels)
-  DS d_;
-  std::map<std::string, Buf> bufs_;
-  u64 total_bytes_ = 0;
-  u64 egress_alloc_ = 0;
-  int ref_back_ = -1;    // egress by reference: steps back a body may be referenced (-1 off)
-  u32 ref_min_ = 256;    // smallest referenced body (smaller ones are cheaper inline)
-  u32 ntiles_max_ = 0;
-  u32 restore_max_ = 0;
-  u64 carry_budget_ = 0;
-  u64 get_cap_ = 0;
-  u8* get_out_dev_ = nullptr;
-  GetRes* get_res_dev_ = nullptr;
-  u64* scan_status_ = nullptr;
-  unsigned long long* spill_moved_ = nullptr;
-  u32* scan_ctl_ = nullptr;
-  u32 scan_smax_ = 0;
-  bool graph_enabled_ = true;
-  bool sdma_ = true;
-  hipGraphExec_t graph_exec_[NPAR_MAX] = {};
-  hipGraphExec_t graph_b_[NPAR_MAX] = {};
-  hipEvent_t ev_a_[NPAR_MAX], ev_ext_[NPAR_MAX];
-  bool phase_a_[NPAR_MAX] = {};
-  bool counts_ready_[NPAR_MAX] = {};
-  bool lag_ = false;
-  std::vector<u32> lag_recv_;
-  u64 lag_stream_ = 0;
-  bool xfer_set_ = false;
-  // native exchange
-  bool native_x_ = false;
-  bool b_due_[NPAR_MAX] = {};   // phase A launched, phase B not yet (native exchange)
-  std::unique_ptr<cmqx::RcclXchg> rccl_;
-  std::unique_ptr<cmqx::ShmXchg> shm_;
-  std::unique_ptr<cmqx::ShmXchg> cshm_;   // rccl + host shared-memory count exchange
-  std::vector<int> xmembers_;
-  int xtimeout_ms_ = 10000;
-  bool xfailover_ = false;
-  bool x_wait_ = false;              // phase B waits on the RCCL bulk transfer
-  u64 xseq_ = 0;
-  // asynchronous exchange (xchg_setup async=true): one job at a time on the exchange thread
-  bool async_x_ = false;
-  std::thread xth_;
-  std::mutex xmu_;
-  std::condition_variable xcv_;
-  bool xstop_ = false, xjob_ = false, xbusy_ = false, xres_ = false;
-  int xq_ = 0, xres_rc_ = 0;
-  u32 xflags_ = 0, xres_orf_ = 0, xjob_seq_ = 0, xseq_job_ = 0;
-  std::string xerr_;
-  u32 b_wait_[NPAR_MAX] = {};           // launch_b(p): the job phase B of parity p waits for (0: none)
-  u32* xflag_h_ = nullptr;           // host-mapped [0] last finished job, [1] a device wait gave up
-  std::mutex cap_mu_;                // graph captures vs the exchange thread's HIP calls
-  hipStream_t s_x_ = nullptr;        // the shared-memory exchange's copies
-  std::mutex io_mu_;
-  hipStream_t s_io_ = nullptr;       // upload / download
-  u32* xflag_d_ = nullptr;
-  u8* xs_desc_[2] = {nullptr, nullptr};
-  u8* xs_pay_[2] = {nullptr, nullptr};
-  u8* xr_desc_[2] = {nullptr, nullptr};
-  u8* xr_pay_[2] = {nullptr, nullptr};
-  bool links_ = false;
-  u8* ls_desc_[2] = {nullptr, nullptr};
-  u8* ls_pay_[2] = {nullptr, nullptr};
-  u8* lk_send_[2] = {nullptr, nullptr};
-  u8* rack_[2] = {nullptr, nullptr};
-  struct HostIO : DS {   // per-parity device view + host addresses of its mapped outputs
-    const Counters* ctr_host_h = nullptr;
-    const SegOut* seg_out_hh = nullptr;
-    const ConnOut* conn_out_hh = nullptr;
-    const CtrlRec* ctrl_rec_hh = nullptr;
-    const u8* ctrl_hh = nullptr;
-    const u8* persist_hh = nullptr;
-    const ConsumedRec* crec_hh = nullptr;
-    const RingMove* grow_hh = nullptr;
-    const u32* conn_conf_hh = nullptr;
-    const GetOut* get_out_hh = nullptr;
-  };
-  std::vector<GetReq> pend_gets_;   // Basic.Get requests for the next submit
-  // deferred control writes: device address -> bytes (non-overlapping), channels to mark
-  static constexpr u64 DELTA_CAP = 4ull << 20;
-  std::mutex dl_mu_;
-  // open: a light control section is still staging into it (stage_begin .. stage_end); a
-  // step never takes an open batch, so one section's change set rides one step whole
-  struct DlBatch { std::map<u64, std::string> w; std::vector<u32> dirty, unp; u64 bytes = 0; bool open = false; u64 id = 0; };
-  std::vector<u32> unp_ready_;   // unpauses of batches flush_deltas applied (next step)
-  u32 spill_req_[3] = {0, 0, 0};   // stage_spill for the next submitted step (dl_mu_)
-  // staged writes with the unpauses staged after them; a batch that overflows one step's
-  // delta buffer keeps its unpauses until its last write is packed
-  std::deque<DlBatch> dl_;
-  u32 dl_open_ = 0;   // light sections staging now (stage_begin / stage_end)
-  u64 dl_next_id_ = 1;   // id of the next batch (DlBatch.id)
-  u64 dl_bytes_ = 0;
-  u8* dl_h_[NPAR_MAX] = {};
-  u32 dl_step_[NPAR_MAX] = {};
-  u64 dl_steps_ = 0;
-  static constexpr u32 COLD_BATCH = 1u << 16;   // cold records per pick / scan call
-  struct Side { int kind; u32 a; u64 b, c; u32 max_n; u64 max_bytes; u32 n; bool launched; };
-  Side side_{SIDE_NONE, 0, 0, 0, 0, 0, 0, false};
-  std::mutex side_mu_;
-  std::condition_variable side_cv_;
-  hipEvent_t ev_side_ = nullptr;
-  void* side_h_ = nullptr;      // host-mapped: [count @0][ColdRec[] @64]
-  void* side_d_ = nullptr;
-  i64* side_live_h_ = nullptr;
-  ColdRec* cold_recs_ = nullptr;
-  u32* cold_cnt_ = nullptr;
-  unsigned long long* cold_bytes_ = nullptr;
-  u64* cold_end_ = nullptr;
-  // overlapped steps (world 1)
-  bool overlap_ = false;
-  int npar_ = 2;   // per-step IO sets in use (NPAR_MAX arrays)
- public:
-  u32 dcap_bytes_ = 0;   // StepIn.dcap_bytes of the next submitted steps (deliver_cap_bytes)
- private:
-  hipStream_t s_ing_ = nullptr;
-  hipEvent_t ev_ing_[NPAR_MAX], ev_rest_[NPAR_MAX];
-  bool rest_issued_[NPAR_MAX] = {}, ing_issued_[NPAR_MAX] = {};
-  bool eager_d2h_[NPAR_MAX] = {};   // the step's egress copy was queued at launch (copy_mode 2)
-  bool pre_[NPAR_MAX] = {};
-  u8* ingress_slot_[INGRESS_SLOTS] = {};
-  u8* work_p1_ = nullptr;
-  hipEvent_t ev_ing_slot_[INGRESS_SLOTS];
-  bool ing_slot_issued_[INGRESS_SLOTS] = {};
-  u64 launch_seq_[NPAR_MAX] = {};          // the step number staged in each parity
-  u64 pre_ptr_[NPAR_MAX] = {}, pre_len_[NPAR_MAX] = {}, pre_seq_[NPAR_MAX] = {};
-  hipEvent_t ev_pre_[NPAR_MAX];
-  hipStream_t s_pre_ = nullptr;
-  hipGraphExec_t graph_ing_[NPAR_MAX] = {};
-  hipGraphExec_t graph_rest_[NPAR_MAX] = {};
-  u64* scan_status_ing_ = nullptr;
-  u32* scan_ctl_ing_ = nullptr;
-  // parity 1's copies of the per-step buffers (parity 0 keeps d_'s)
-  std::vector<std::function<void(DS&)>> par1_;
-  template <class T>
-  void dup(T* DS::*m, const char* name, size_t bytes) {
-    T* p1 = (T*)alloc((std::string(name) + "_p1").c_str(), bytes, false);
-    par1_.push_back([m, p1](DS& io) { io.*m = p1; });
-  }
-  GetReq* stage_gets_[NPAR_MAX] = {};
-  u32* stage_unp_[NPAR_MAX] = {};
-  u32 nunp_[NPAR_MAX] = {};   // unpauses the last submit on each parity carried
-  u32 nget_[NPAR_MAX] = {};
-  HostIO io_[NPAR_MAX];
-  CmqEngineApi api_{};
-  std::string err_;
-  u8* egress_dev_[EGRESS_SLOTS] = {};
-  u8* egress_host_[EGRESS_SLOTS] = {};
-  u8* egress_host_dev_[EGRESS_SLOTS] = {};
-  int slot_of_[NPAR_MAX] = {};
-  int pslot_of_[NPAR_MAX] = {};
-  int copy_mode_ = 0;
-  hsa_agent_t gpu_agent_{}, cpu_agent_{};
-  hsa_amd_sdma_engine_id_t sdma_engine_{}, sdma_engine2_{};
-  int sdma_split_ = 1;
-  hsa_signal_t sdma_sig_[EGRESS_SLOTS] = {};
-  bool sdma_pending_[EGRESS_SLOTS] = {};
-  // gated egress: per slot the gate the step's last kernel opens, the host tail's signal,
-  // whether a tail is in flight and the bytes copied speculatively for the slot's step
-  bool gated_ = false;
-  hsa_signal_t gate_sig_[EGRESS_SLOTS] = {};
-  u64 spin_ticks_ = 0, block_ticks_ = 0;   // bounded_wait: active spin / blocked slice (timestamp ticks)
-  u32 wait_ms_ = 10000;                    // bounded_wait deadline
-  bool wait_failed_ = false, gate_fault_ = false;
-  void* gate_dummy_ = nullptr;             // device word a faulted step's gate store lands in
-  hsa_signal_t tail_sig_[EGRESS_SLOTS] = {};
-  bool tail_pending_[EGRESS_SLOTS] = {};
-  u64 spec_[EGRESS_SLOTS] = {};
-  hsa_amd_sdma_engine_id_t tail_engine_{};
-  u64 eg_hist_[4] = {0, 0, 0, 0};
-  u32 eg_hist_i_ = 0;
-  u64 eg_stats_[4] = {0, 0, 0, 0};
-  u32 copy_wgs_ = 16;
-  int sdma_pref_ = -1;
-  double ht_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // host_times() phases
-  StepIn* stage_in_[NPAR_MAX] = {};
-  SegIn* stage_segs_[NPAR_MAX] = {};
-  hipStream_t s_comp_ = nullptr, s_h2d_ = nullptr, s_d2h_ = nullptr;
-  hipStream_t s_h2d_alt_ = nullptr;   // odd steps' H2D (cfg h2d_alt)
-  hipStream_t h2d_of(u64 step) const { return (s_h2d_alt_ && (step & 1)) ? s_h2d_alt_ : s_h2d_; }
-  // cfg h2d_hsa: ingress payloads in GPU-mapped host memory go to the SDMA engine through HSA
-  bool h2d_hsa_ = false;
-  hsa_amd_sdma_engine_id_t ing_engine_{};
-  hsa_signal_t ing_sig_[INGRESS_SLOTS] = {};
-  bool ing_hsa_[INGRESS_SLOTS] = {};   // the slot's last payload went through HSA (ing_sig_)
-  bool h2d_hip_[NPAR_MAX] = {true, true, true};   // the step's stream waits for ev_h2d_
-  u64 h2d_addr_[NPAR_MAX] = {};   // the word the step's k_h2d_wait polled (0: none)
-  u64 h2d_addr2_[NPAR_MAX] = {};  // (and its second half's, a split payload)
-  hsa_amd_sdma_engine_id_t ing_engine2_{};   // a split payload's second engine (0: no split)
-  hsa_signal_t ing_sig2_[INGRESS_SLOTS] = {};
-  bool ing_split_[INGRESS_SLOTS] = {};
-  bool h2d_fault_ = false;
-  bool h2d_split_cfg_ = false;
-  u64 h2d_split_min_ = 4u << 20;
-  void* h2d_dummy_ = nullptr;     // pinned host word of inject_h2d_fault
-
-  // the agent address of a payload in page-locked host memory (hipHostMalloc /
-  // hipHostRegister), 0 for pageable memory (the runtime's copy stages that)
-  static u64 ingress_src(u64 ptr) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, (const void*)ptr) != hipSuccess) {
-      (void)hipGetLastError();
-      return 0;
-    }
-    return a.type == hipMemoryTypeHost && a.devicePointer ? (u64)a.devicePointer : 0;
-  }
-
-  // a step's payload into ingress slot is: on the HSA path (k_h2d_wait waits for it on the
-  // device) or as a runtime copy on stream ps (the step's stream waits for ev_h2d_)
-  void ingress_copy(u64 step, int is, u64 ptr, u64 len, hipStream_t ps) {
-    const u64 src = h2d_hsa_ ? ingress_src(ptr) : 0;
-    if (src) {
-      // the slot's last reader (step - INGRESS_SLOTS, collected long ago in the drivers'
-      // order) and its copy are done before the signal is re-armed
-      if (step >= INGRESS_SLOTS && ing_slot_issued_[is] && hipEventQuery(ev_ing_slot_[is]) != hipSuccess)
-        HIPCHECK(hipEventSynchronize(ev_ing_slot_[is]));
-      if (ing_hsa_[is]) bounded_wait(ing_sig_[is], -1, "ingress H2D");
-      if (ing_split_[is]) bounded_wait(ing_sig2_[is], -1, "ingress H2D");
-      // a large payload in two halves on two engines at once: 56.8 vs 54.9 GB/s on one (the
-      // PCIe link is the bound, bench/micro/h2d_chain_probe.hip, profiles/r6_z/h2d_chain3.txt)
-      const bool split = ing_engine2_ && len >= h2d_split_min_ && len > 8192;
-      const u64 h1 = split ? ((len / 2 + 4095) & ~u64(4095)) : len;
-      hsa_signal_store_relaxed(ing_sig_[is], 1);
-      if (hsa_amd_memory_async_copy_on_engine(ingress_slot_[is], gpu_agent_, (const void*)src, cpu_agent_, h1, 0,
-                                              nullptr, ing_sig_[is], ing_engine_, true) != HSA_STATUS_SUCCESS)
-        throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (ingress) failed");
-      if (split) {
-        hsa_signal_store_relaxed(ing_sig2_[is], 1);
-        if (hsa_amd_memory_async_copy_on_engine(ingress_slot_[is] + h1, gpu_agent_, (const void*)(src + h1), cpu_agent_,
-                                                len - h1, 0, nullptr, ing_sig2_[is], ing_engine2_,
-                                                true) != HSA_STATUS_SUCCESS)
-          throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (ingress, second half) failed");
-      }
-      ing_hsa_[is] = true;
-      ing_split_[is] = split;
-      return;
-    }
-    if (step >= INGRESS_SLOTS && ing_slot_issued_[is] && hipEventQuery(ev_ing_slot_[is]) != hipSuccess)
-      HIPCHECK(hipStreamWaitEvent(ps, ev_ing_slot_[is], 0));
-    HIPCHECK(hipMemcpyAsync((void*)ingress_slot_[is], (const void*)ptr, len,
-                            sdma_ ? hipMemcpyDeviceToDeviceNoCU : hipMemcpyHostToDevice, ps));
-    ing_hsa_[is] = false;
-    ing_split_[is] = false;
-  }
-  hipEvent_t ev_h2d_[NPAR_MAX], ev_done_[NPAR_MAX], ev_d2h_[EGRESS_SLOTS];
-  bool inflight_[NPAR_MAX] = {};
-  bool staged_[NPAR_MAX] = {};   // submitted with defer, kernels not launched yet
-  bool d2h_issued_[EGRESS_SLOTS] = {};
-  u64 seq_ = 0;
 };
 
 static py::array alloc_pinned(size_t bytes) {

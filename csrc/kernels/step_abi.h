@@ -113,6 +113,12 @@ struct GetReq { u32 conn; u32 chslot; u32 q; u32 noack; };
 enum : u32 { GS_EMPTY = 0, GS_OK = 1, GS_RETRY = 2, GS_NO_SPACE = 3, GS_WINDOW_FULL = 4, GS_GONE = 5 };
 struct GetOut { u32 status; u32 msg_count; };
 
+// deferred control writes carried by a step (delta_stage.h packs, k_stage applies):
+//   DeltaHead | DeltaRec[nrec] | u32 dirty channel slots[ndirty] (16-B padded) | data chunks
+struct DeltaHead { u32 nrec, ndirty, nchunk, pad; };
+struct DeltaRec { u64 dst; u32 len; u32 chunk0; };
+#define DELTA_REC_MAX 1024   // records per step (the host keeps the rest for later steps)
+
 // C entry points of one Engine (engine.hip: Engine::c_api).  All return 0 / a parity on
 // success and -1 on error (message: error()).  Parity p = the double-buffered step IO set
 // of a submitted step; its host-mapped outputs stay valid until the next submit of p.

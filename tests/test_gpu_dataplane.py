@@ -256,3 +256,104 @@ def test_lost_ingress_copy_fails_loudly(gpu):
         d.step({0: publish_stream(20, "hx", lambda i: "", 512, seed=99)})
     assert d.eng.wait_failed()
     del d
+
+
+# graph, engine cfg, payloads queued ahead with prefetch
+PIPELINED = {
+    "overlap-prefetch": (True, {}, 2),
+    "par3": (True, {"overlap": 0, "parities": 3}, 0),
+    "par3-eager": (False, {"overlap": 0, "parities": 3}, 0),
+    "h2d-alt": (True, {"overlap": 0, "h2d_alt": 1}, 0),
+    "hsa-par3": (True, {"copy_engine": 3, "overlap": 0, "h2d_hsa": 1, "parities": 3}, 1),
+    "hsa-ungated": (True, {"copy_engine": 3, "overlap": 0, "egress_gate": 0}, 0),
+}
+INGRESS_SLOTS = 3       # the engine rotates three ingress payload buffers (dp_state.h)
+PIPELINED_STEPS = 13   # wraps the 2- and 3-parity, 3-ingress-slot and 4-egress-slot rotations (lcm 12) once
+
+
+def _pipelined_plane(cls, **kw):
+    d = cls(**kw)
+    vh = "AMQ.DEFAULT"
+    d.declare_queue(vh, "pq")
+    for c in (0, 1):
+        d.open_connection(c, vh)
+        d.open_channel(c, 1)
+    d.consume(1, 1, vh, "pq", "c", no_ack=True)
+    return d
+
+
+@pytest.fixture(scope="module")
+def pipelined_golden():
+    """(streams, the consumer's golden egress per step): computed once, only read by the cases."""
+    from chanamq_amd.engine.golden import GoldenDataPlane
+    from chanamq_amd.engine.traffic import publish_stream
+    from dp_scenarios import NOW
+
+    g = _pipelined_plane(GoldenDataPlane, c_max=CFG["c_max"], chpc=CFG["chpc"], q_max=CFG["q_max"],
+                         x_max=CFG["x_max"], cons_max=CFG["cons_max"], ucap=CFG["ucap"], carry_cap=CFG["carry_cap"],
+                         default_queue_capacity=CFG["default_queue_capacity"])
+    streams = [publish_stream(8, "", lambda i: "pq", 64, seed=100 + k) for k in range(PIPELINED_STEPS)]
+    want = [g.step({0: s}, now_ms=NOW + k)["egress"].get(1, b"") for k, s in enumerate(streams)]
+    assert all(want)
+    return streams, want
+
+
+@pytest.mark.parametrize("variant", sorted(PIPELINED))
+def test_pipelined_io_variants_match_golden(gpu, variant, pipelined_golden):
+    """Several parities in flight (submit_raw / finish, ``parities`` steps outstanding) on the IO
+    paths the synchronous golden matrix never takes -- prefetch, three parities, the alternate
+    H2D stream, HSA ingress with prefetch, ungated HSA egress: every step's egress is byte-equal
+    to the golden model's."""
+    import numpy as np
+
+    from chanamq_amd.engine.dataplane import GpuDataPlane
+    from chanamq_amd.engine.layout import SEG_IN
+    from dp_scenarios import NOW
+
+    graph, cfg, ahead = PIPELINED[variant]
+    streams, want = pipelined_golden
+    d = _pipelined_plane(GpuDataPlane, graph=graph, **cfg, **CFG)
+    if cfg.get("parities") == 3:
+        assert d.info["parities"] == 3
+    if cfg.get("h2d_hsa"):
+        assert d.info["h2d_hsa_engine"] >= 0
+    # each step's bytes in their own 16-byte-aligned region of one page-locked pool
+    region = (max(len(s) for s in streams) + 15) & ~15
+    pool = d.mod.alloc_pinned(region * len(streams))
+    assert pool.ctypes.data % 16 == 0
+    segs = []
+    for k, s in enumerate(streams):
+        pool[k * region:k * region + len(s)] = np.frombuffer(s, np.uint8)
+        sg = np.zeros(1, SEG_IN)
+        sg[0] = (0, len(s), 0)
+        segs.append(sg)
+    ptr = lambda k: pool.ctypes.data + k * region
+    plen = lambda k: (len(streams[k]) + 15) & ~15
+    queued, submitted, finished = [-1], [0], [-1]   # last step prefetched / steps submitted / last step finished
+
+    def prefetch_ahead():
+        # the payloads of the next `ahead` steps to submit, each as soon as the engine's contract
+        # allows: its ingress slot's last user (three steps back) has been collected
+        for t in range(submitted[0], min(submitted[0] + ahead, len(streams))):
+            if t > queued[0] and t - INGRESS_SLOTS <= finished[0]:
+                assert d.prefetch(ptr(t), plen(t)) is True, f"prefetch of step {t}"
+                queued[0] = t
+
+    tickets = {}
+
+    def submit(k):
+        tickets[k] = d.submit_raw(segs[k], ptr(k), plen(k), now_ms=NOW + k)
+        submitted[0] = k + 1
+        prefetch_ahead()
+
+    prefetch_ahead()
+    for k in range(min(d.parities - 1, len(streams))):
+        submit(k)
+    for k in range(len(streams)):
+        if k + d.parities - 1 < len(streams):
+            submit(k + d.parities - 1)
+        r = d.finish(tickets.pop(k))
+        finished[0] = k
+        prefetch_ahead()
+        assert r.counters["n_deliv"] == 8, f"step {k}"
+        assert r.egress.get(1, b"") == want[k], f"step {k} egress differs"
