@@ -143,6 +143,9 @@ class GpuDataPlane(ControlState):
                 self.eng.set_xfer_buffers(self._xs[0][0].data_ptr(), self._xs[0][1].data_ptr(),
                                           self._xr[0][0].data_ptr(), self._xr[0][1].data_ptr())
         self._deleted_rings = {}
+        # bounds of the device's exchange-to-exchange walk (control.py checks them at bind time)
+        self.hop_qmax, self.hop_xslots, self.hopx_max = i["hop_qmax"], i["hop_xslots"], i["hopx_max"]
+        self.tb_max = i["tb_max"]
         super().__init__(c_max=i["c_max"], chpc=i["chpc"], q_max=i["q_max"], x_max=i["x_max"],
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
@@ -197,6 +200,10 @@ class GpuDataPlane(ControlState):
         x_t_off = np.zeros(self.x_max, np.uint32)
         x_t_n = np.zeros(self.x_max, np.uint32)
         fan_q, d_q = [], []
+        # exchange-to-exchange edges (x_type bit 8 = the exchange has outgoing edges)
+        x_fanx_off = np.zeros(self.x_max, np.uint32)
+        x_fanx_n = np.zeros(self.x_max, np.uint32)
+        fan_x, d_x = [], []
         kpool = bytearray()
         dh = i["dhash"]
         d_key = np.zeros(dh, np.uint64)
@@ -205,6 +212,8 @@ class GpuDataPlane(ControlState):
         d_kb_len = np.zeros(dh, np.uint32)
         d_q_off = np.zeros(dh, np.uint32)
         d_q_n = np.zeros(dh, np.uint32)
+        d_x_off = np.zeros(dh, np.uint32)
+        d_x_n = np.zeros(dh, np.uint32)
         tb = []   # (exch, queue, pattern)
         for x in sorted(self.exchanges.values(), key=lambda e: e.slot):
             h = exch_hash(self.vhosts[x.vhost], x.name.encode())
@@ -216,17 +225,25 @@ class GpuDataPlane(ControlState):
                     break
             else:
                 raise ControlError(C.RESOURCE_ERROR, "exchange hash full")
-            x_type[x.slot] = C.EXCHANGE_TYPE_ID[x.type]
+            x_type[x.slot] = C.EXCHANGE_TYPE_ID[x.type] | (0x100 if x.xbindings else 0)
             if x.type == "fanout":
                 qs = sorted({q for q, _ in x.bindings})
                 x_fan_off[x.slot] = len(fan_q)
                 x_fan_n[x.slot] = len(qs)
                 fan_q.extend(qs)
+                xs = sorted({s for s, _ in x.xbindings})
+                x_fanx_off[x.slot] = len(fan_x)
+                x_fanx_n[x.slot] = len(xs)
+                fan_x.extend(xs)
             elif x.type == "direct":
                 by_key = defaultdict(list)
                 for q, k in x.bindings:
                     if q not in by_key[k]:
                         by_key[k].append(q)
+                xby_key = defaultdict(set)
+                for s, k in x.xbindings:
+                    xby_key[k].add(s)
+                    by_key[k]   # (a key with edges and no queues still gets a slot)
                 for k, qs in by_key.items():
                     dk = direct_key(fnv1a64(k), x.slot)
                     for j in range(dh):
@@ -243,14 +260,22 @@ class GpuDataPlane(ControlState):
                     d_q_off[s] = len(d_q)
                     d_q_n[s] = len(qs)
                     d_q.extend(sorted(qs))
+                    d_x_off[s] = len(d_x)
+                    d_x_n[s] = len(xby_key.get(k, ()))
+                    d_x.extend(sorted(xby_key.get(k, ())))
             else:  # topic, headers (routes as topic: ExchangeEntity.scala:149-154)
                 x_t_off[x.slot] = len(tb)
                 bs = sorted(set(x.bindings))
+                # edges: rows after the queues', sorted by destination, the destination slot
+                # under the top bit of t_queue
+                bs += sorted({(0x80000000 | s, k) for s, k in x.xbindings})
                 x_t_n[x.slot] = len(bs)
                 tb.extend((x.slot, q, k) for q, k in bs)
         tbp = i["tb_pad"]
         if len(tb) > i["tb_max"]:
             raise ControlError(C.RESOURCE_ERROR, "too many topic bindings for the GPU table")
+        if max(len(fan_x), len(d_x)) > i["hopx_max"]:
+            raise ControlError(C.RESOURCE_ERROR, "too many exchange-to-exchange bindings")
         t_queue = np.zeros(tbp, np.uint32)
         t_exch = np.zeros(tbp, np.uint32)
         t_kb_off = np.zeros(tbp, np.uint32)
@@ -268,7 +293,8 @@ class GpuDataPlane(ControlState):
             t_mat[n] = row
         for name, arr in (("x_hkey", x_hkey), ("x_hval", x_hval), ("x_type", x_type),
                           ("x_fan_off", x_fan_off), ("x_fan_n", x_fan_n), ("x_t_off", x_t_off),
-                          ("x_t_n", x_t_n), ("d_key", d_key), ("d_exch", d_exch), ("d_kb_off", d_kb_off),
+                          ("x_t_n", x_t_n), ("x_fanx_off", x_fanx_off), ("x_fanx_n", x_fanx_n),
+                          ("d_x_off", d_x_off), ("d_x_n", d_x_n), ("d_key", d_key), ("d_exch", d_exch), ("d_kb_off", d_kb_off),
                           ("d_kb_len", d_kb_len), ("d_q_off", d_q_off), ("d_q_n", d_q_n),
                           ("t_queue", t_queue), ("t_exch", t_exch), ("t_kb_off", t_kb_off),
                           ("t_kb_len", t_kb_len), ("t_flags", t_flags), ("t_expect", t_expect),
@@ -279,6 +305,10 @@ class GpuDataPlane(ControlState):
             self._up_diff("fan_q", np.array(fan_q, np.uint32))
         if d_q:
             self._up_diff("d_q", np.array(d_q, np.uint32))
+        if fan_x:
+            self._up_diff("fan_x", np.array(fan_x, np.uint32))
+        if d_x:
+            self._up_diff("d_x", np.array(d_x, np.uint32))
         if kpool:
             self._up_diff("kpool", np.frombuffer(bytes(kpool), np.uint8))
 

@@ -769,6 +769,11 @@ class GoldenDataPlane(ControlState):
             ring.append((msg, False, e))
 
     def _route(self, x, rk):
+        if x.xbindings:   # exchange-to-exchange edges: the closure, each exchange matched once
+            return self.route_closure(x, rk, self._route_flat)
+        return self._route_flat(x, rk)
+
+    def _route_flat(self, x, rk):
         if x.type == "direct":
             seen = []
             for q, k in x.bindings:

@@ -13,6 +13,7 @@ from ..protocol import constants as C
 from .comm import Comm
 
 REPLICATED = {"declare_exchange", "delete_exchange", "declare_queue", "delete_queue", "bind", "unbind",
+              "bind_exchange", "unbind_exchange",
               "place_queue", "ensure_vhost", "link_open", "link_close", "link_pull", "link_got", "big_publish"}
 
 

@@ -18,8 +18,10 @@ staged by the front end; the broker handles Get and its answer without pausing t
 stepper); the other front ends run it between steps (k_basic_get).  Transactions: on a Tx
 channel the device hands publishes / acks to the host instead of applying them
 (CK_TXBUF); Tx.Commit applies the acks between steps and injects the publishes through a
-pseudo-connection in the next step, Tx.Rollback drops them.  Not on the GPU path yet
-(540 NOT_IMPLEMENTED; the host-path broker in csrc/core serves it): Exchange.Bind/Unbind.
+pseudo-connection in the next step, Tx.Rollback drops them.  Exchange.Bind / Unbind
+(exchange-to-exchange bindings, walked by the data plane per publish) are served with
+``exchange_bindings=True`` (chana.mq.gpu.exchange-bindings); off, the default: 540
+NOT_IMPLEMENTED and the capability flag false.
 Sharded: consumers and Basic.Get may name a queue another rank owns (parallel/links.py).
 """
 
@@ -45,6 +47,7 @@ HEARTBEAT = C.HEARTBEAT_FRAME
 _REPLICATED_METHODS = {"exchange.declare", "exchange.delete", "queue.declare", "queue.bind", "queue.unbind",
                        "queue.delete"}
 _STORED_METHODS = _REPLICATED_METHODS
+_EDGE_METHODS = {"exchange.bind", "exchange.unbind"}   # replicated when served; never stored
 
 
 class _Conn:
@@ -216,13 +219,16 @@ class GpuBroker:
                  ingress_bytes=64 << 20, per_conn_read=256 << 10, mem_high_watermark=None, mem_low_watermark=None,
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
-                 persist_group_ms=2.0):
+                 persist_group_ms=2.0, exchange_bindings=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
         gateway.cpp), "python" = selectors loop (portable fallback); "auto" = pipeline
         for a single-rank GPU plane, else native."""
         self.plane = plane
+        # Exchange.Bind / Exchange.Unbind (exchange-to-exchange bindings, routed by the data
+        # plane's closure walk): served and advertised when on, 540 NOT_IMPLEMENTED when off
+        self.exchange_bindings = bool(exchange_bindings)
         native_x = bool(getattr(plane, "native_xchg", False))
         if io == "auto":
             io = "pipeline" if (hasattr(plane, "eng") and (node is None or native_x)) else "native"
@@ -1035,7 +1041,8 @@ class GpuBroker:
                 self._drop(c)
                 return b""
             del c.inbuf[:8]
-            caps = {"publisher_confirms": True, "exchange_exchange_bindings": False, "basic.nack": True,
+            caps = {"publisher_confirms": True, "exchange_exchange_bindings": self.exchange_bindings,
+                    "basic.nack": True,
                     "consumer_cancel_notify": True, "connection.blocked": False}
             self._send(c, 0, Method("connection.start", version_major=0, version_minor=9,
                                     server_properties={"product": self.product, "version": self.version,
@@ -1326,7 +1333,8 @@ class GpuBroker:
         if m.name == "basic.publish":   # the device hands over only publishes larger than its carry
             return self._big_begin(c, ch, m, raw, size)
         try:
-            if self.node is not None and m.name in _REPLICATED_METHODS:
+            if self.node is not None and (m.name in _REPLICATED_METHODS or
+                                          (m.name in _EDGE_METHODS and self.exchange_bindings)):
                 return self._replicated(c, ch, m)
             r = self._channel_method(c, ch, m)
             if self.persistence is not None and m.name in _STORED_METHODS:
@@ -1615,6 +1623,14 @@ class GpuBroker:
             if self.persistence is not None:
                 self.persistence.unbind(vh, qn, m.exchange, m.routing_key)
             self._send(c, ch, Method("queue.unbind_ok"))
+        elif n in _EDGE_METHODS and self.exchange_bindings:
+            # (arguments are accepted and ignored; edges are not written to the store)
+            if n == "exchange.bind":
+                p.bind_exchange(vh, m.destination, m.source, m.routing_key)
+            else:
+                p.unbind_exchange(vh, m.destination, m.source, m.routing_key)
+            if not m.nowait:
+                self._send(c, ch, Method(n + "_ok"))
         elif n == "queue.purge":
             q = self._queue(vh, m.queue or c.last_queue.get(ch, ""), 50, 30)
             cnt = p.purge(q.slot)
@@ -1770,6 +1786,10 @@ class GpuBroker:
             seq = node.submit("bind" if n == "queue.bind" else "unbind", vh, qn, m.exchange, m.routing_key)
             ok = "queue.bind_ok" if n == "queue.bind" else "queue.unbind_ok"
             reply = None if (n == "queue.bind" and m.nowait) else (lambda r, ok=ok: Method(ok))
+        elif n in _EDGE_METHODS:
+            seq = node.submit("bind_exchange" if n == "exchange.bind" else "unbind_exchange", vh, m.destination,
+                              m.source, m.routing_key)
+            reply = None if m.nowait else (lambda r, ok=n + "_ok": Method(ok))
         else:   # queue.delete
             q = self._queue(vh, m.queue or c.last_queue.get(ch, ""), 50, 40)
             if m.if_unused and q.consumers:

@@ -292,6 +292,7 @@ class Config:
                       idle_step_ms=float(g(k + "idle-step-ms", 1.0)), per_conn_read=int(g(k + "per-conn-read", 512 << 10)),
                       confirm_read=int(g(k + "confirm-read", 128 << 10)),
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
+                      exchange_bindings=bool(g(k + "exchange-bindings", False)),
                       mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 

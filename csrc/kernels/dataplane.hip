@@ -450,6 +450,7 @@ __global__ __launch_bounds__(1024) void k_stage(DS d) {
       d.ctr->n_grow = 0; d.tot[TS_NMOVE] = 0; d.tot[TS_NDEFER] = 0; d.tot[TS_TTL_BUDGET] = 0;
       d.tot[TS_NDGET] = 0;
       d.tot[TS_SPILL_USED] = 0;
+      d.tot[TS_HOP_N] = 0;
       d.ctr->spill_moved = 0;
       d.ctr->n_ref = 0; d.ctr->gath_off = 0; d.ctr->ref_bytes = 0;
       *d.egress_budget = 0;
@@ -2285,14 +2286,14 @@ DEV bool topic_verify(const DS& d, const Pub& pb, u32 pidx, u32 t, u32 fl) {
   return diff == 0;
 }
 
-DEV i32 direct_find(const DS& d, const Pub& pb) {
-  u64 k = pb.keyhash ^ (u64(pb.exch) * 0x9E3779B97F4A7C15ULL);
+DEV i32 direct_find(const DS& d, const Pub& pb, i32 exch) {
+  u64 k = pb.keyhash ^ (u64(exch) * 0x9E3779B97F4A7C15ULL);
   u32 mask = d.dhash_mask;
   for (u32 j = 0; j <= mask; ++j) {
     u32 s = (u32)(k + j) & mask;
     i32 ex = d.d_exch[s];
     if (ex < 0) return -1;
-    if (ex == pb.exch && d.d_key[s] == k &&
+    if (ex == exch && d.d_key[s] == k &&
         word_eq(d.kpool + d.d_kb_off[s], d.d_kb_len[s], pub_src(d, pb) + pb.rk_off, pb.rk_len))
       return (i32)s;
   }
@@ -2350,6 +2351,91 @@ DEV void route_emit(const DS& d, RouteAcc<PASS>& a, u32 p, u32 wbase, u32 srank,
   a.nq_all += (u32)__popcll(__ballot(valid));
 }
 
+// ---- exchange-to-exchange bindings: a publish whose entry exchange has outgoing edges
+// (x_type & XF_HOP) walks the closure in route pass 0, one wave per publish, through the
+// same matchers as every other publish (route_one's loop runs once per visited exchange).
+// Visited and pending exchanges are one register each across the wave (lane l: slots
+// 32l .. 32l+31); the pending exchange with the lowest slot is matched next and every
+// exchange once, so cycles end.  Matching queues collect in a per-wave LDS list (distinct;
+// the host keeps every walk's reach within HOP_QMAX at bind time) and go through route_emit
+// when the walk is over, so everything downstream of the queue set is the plain path's.
+// With more than 8 local queues the local list is also kept in hop_q for pass 1.
+struct HopWalk {
+  u32* L;            // the wave's queue list
+  u32 nl = 0;        // queues in it
+  u32 visited = 0, pending = 0;
+};
+
+// one candidate per lane: a queue (appended unless listed) or XT_EDGE | destination exchange
+DEV void hop_add(HopWalk& h, u32 item, bool valid, u32 lane) {
+  const bool isx = valid && (item & XT_EDGE);
+  bool isq = valid && !isx;
+  if (isq)
+    for (u32 i = 0; i < h.nl; ++i)
+      if (h.L[i] == item) { isq = false; break; }
+  const u64 qm = __ballot(isq);
+  const u32 pos = h.nl + (u32)__popcll(qm & lanemask_lt());
+  if (isq && pos < HOP_QMAX) h.L[pos] = item;
+  h.nl += (u32)__popcll(qm);
+  if (h.nl > HOP_QMAX) h.nl = HOP_QMAX;
+  __builtin_amdgcn_wave_barrier();
+  for (u64 xm = __ballot(isx); xm; xm &= xm - 1) {
+    const u32 dst = (u32)__shfl((int)item, (int)(__ffsll((unsigned long long)xm) - 1)) & ~XT_EDGE;
+    if (lane == (dst >> 5) && !((h.visited >> (dst & 31)) & 1)) h.pending |= 1u << (dst & 31);
+  }
+}
+
+// the pending exchange with the lowest slot becomes visited; false when none is left
+DEV bool hop_next(HopWalk& h, u32& x, u32 lane) {
+  const u64 pm = __ballot(h.pending != 0);
+  if (!pm) return false;
+  const u32 l0 = (u32)__ffsll((unsigned long long)pm) - 1;
+  const u32 bit = (u32)__ffs((int)__shfl((int)h.pending, (int)l0)) - 1;
+  if (lane == l0) { h.pending &= ~(1u << bit); h.visited |= 1u << bit; }
+  x = l0 * 32 + bit;
+  return true;
+}
+
+// the walk is over: its queues through route_emit, the local ones kept for pass 1
+DEV void hop_finish(const DS& d, RouteAcc<0>& a, const HopWalk& h, const Pub& pb, u32 p, u32 srank, u32 lane) {
+  __builtin_amdgcn_wave_barrier();
+  for (u32 k0 = 0; k0 < h.nl; k0 += 64) {
+    const bool v = k0 + lane < h.nl;
+    route_emit<0>(d, a, p, 0, srank, v ? h.L[k0 + lane] : 0u, v, lane);
+  }
+  // more than 8 local queues: a run of hop_q for pass 1.  Only a publish that is enqueued
+  // reserves (an immediate publish without a consumer is returned with 313: no pairs), so
+  // the reservations never add up to more than the step's pairs
+  if (a.nq <= 8 || ((pb.flags & (MF_IMMEDIATE | MF_IMPORTED)) == MF_IMMEDIATE && !a.has_cons)) return;
+  u32 off = lane == 0 ? atomicAdd(&d.tot[TS_HOP_N], a.nq) : 0u;
+  off = (u32)__shfl((int)off, 0);
+  if (off + a.nq > d.pair_max) {
+    // no room: the step's pair table overflows as well; as there, not enqueued and the
+    // publisher gets Basic.Nack
+    if (lane == 0) {
+      atomicAdd(&d.ctr->n_ring_full, a.nq);
+      if (pb.chslot != INVALID) d.ch_pub_fail[pb.chslot] = 1u;
+    }
+    a.nq = 0;
+    return;
+  }
+  u32 n = 0;
+  for (u32 k0 = 0; k0 < h.nl; k0 += 64) {
+    const bool v = k0 + lane < h.nl;
+    const u32 q = v ? h.L[k0 + lane] : 0u;
+    const bool local = v && (d.world > 1 ? d.q_owner[q] : d.my_rank) == d.my_rank;
+    const u64 lm = __ballot(local);
+    if (local) d.hop_q[off + n + (u32)__popcll(lm & lanemask_lt())] = q;
+    n += (u32)__popcll(lm);
+  }
+  // pub_qc[0] was stored by route_emit, possibly from another lane: release / acquire at
+  // wavefront scope orders lane 0's store after it
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane == 0) d.pub_qc[(u64)p * 8] = XT_EDGE | off;
+}
+
 template <int PASS>
 DEV void route_one(const DS& d, u32 p, u32 lane) {
   Pub& pb = d.pubs[p];
@@ -2367,10 +2453,14 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
     if (nq0 == 0) return;
     if (wbase >= d.pair_max) return;  // capacity: log_reserve clamps the pair count
     const u32 fit = d.pair_max - wbase < nq0 ? d.pair_max - wbase : nq0;
-    if (nq0 <= 8) {  // routing result cached by pass 0
-      if (lane < fit) {
-        d.pair_k[0][wbase + lane] = (d.pub_qc[(u64)p * 8 + lane] << d.rank_bits) | srank;
-        d.pair_v[0][wbase + lane] = p;
+    // routing result cached by pass 0: up to 8 queues in pub_qc; the longer list of a walk
+    // (exchange-to-exchange edges) in a run of hop_q, its offset under XT_EDGE in pub_qc[0]
+    const u32 q0 = d.pub_qc[(u64)p * 8];
+    if (nq0 <= 8 || (q0 & XT_EDGE)) {
+      const u32* run = nq0 <= 8 ? d.pub_qc + (u64)p * 8 : d.hop_q + (q0 & ~XT_EDGE);
+      for (u32 k = lane; k < fit; k += 64) {
+        d.pair_k[0][wbase + k] = (run[k] << d.rank_bits) | srank;
+        d.pair_v[0][wbase + k] = p;
       }
       return;
     }
@@ -2381,49 +2471,82 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
     route_emit<PASS>(d, a, p, wbase, srank, (u32)pb.keyhash, lane == 0, lane);
   } else if (ex >= 0) {
     u32 xt = d.x_type[ex];
-    if (xt == EX_DIRECT || xt == EX_FANOUT) {
-      u32 o = 0, c = 0;
-      const u32* list;
-      if (xt == EX_DIRECT) {
-        i32 s = lane == 0 ? direct_find(d, pb) : 0;
-        s = __shfl(s, 0);
-        if (s >= 0) { o = d.d_q_off[s]; c = d.d_q_n[s]; }
-        list = d.d_q;
-      } else {
-        o = d.x_fan_off[ex]; c = d.x_fan_n[ex];
-        list = d.fan_q;
-      }
-      for (u32 k0 = 0; k0 < c; k0 += 64) {
-        bool v = k0 + lane < c;
-        u32 q = v ? list[o + k0 + lane] : 0;
-        route_emit<PASS>(d, a, p, wbase, srank, q, v, lane);
-      }
-    } else {
-      u32 o = d.x_t_off[ex], c = d.x_t_n[ex];
-      u32 lastq = INVALID;
-      for (u32 k0 = 0; k0 < c; k0 += 64) {
-        bool v = k0 + lane < c;
-        u32 t = o + k0 + lane;
-        u32 q = INVALID, fl = 0, qo = INVALID, qc = INVALID;
-        bool hit = false;
-        if (v) {
-          q = d.t_queue[t];
-          if (topic_cand(d, pb, p, t, fl)) {
-            // the queue's owner / consumer count load alongside the exact check's loads
-            qo = d.world > 1 ? d.q_owner[q] : d.my_rank;
-            qc = d.q_cons_n[q];
-            hit = topic_verify(d, pb, p, t, fl);
+    // a walk over exchange-to-exchange edges (pass 0; pass 1 was served from pub_qc / hop_q
+    // above): the loop below runs once per visited exchange, candidates go to the walk's list
+    const bool hop = PASS == 0 && __builtin_expect((xt & XF_HOP) != 0, 0);
+    HopWalk h;
+    u32 x = (u32)ex;
+    if (hop) {
+      __shared__ u32 hop_list[16][HOP_QMAX];   // (route pass 0 runs at most 16 waves per block)
+      h.L = hop_list[threadIdx.x >> 6];
+      h.visited = (x >> 5) == lane ? 1u << (x & 31) : 0u;
+      xt &= XF_TYPE;
+    }
+    for (;;) {
+      if (xt == EX_DIRECT || xt == EX_FANOUT) {
+        u32 o = 0, c = 0, xo = 0, xc = 0;
+        const u32* list;
+        if (xt == EX_DIRECT) {
+          i32 s = lane == 0 ? direct_find(d, pb, (i32)x) : 0;
+          s = __shfl(s, 0);
+          if (s >= 0) {
+            o = d.d_q_off[s]; c = d.d_q_n[s];
+            if (hop) { xo = d.d_x_off[s]; xc = d.d_x_n[s]; }
+          }
+          list = d.d_q;
+        } else {
+          o = d.x_fan_off[x]; c = d.x_fan_n[x];
+          if (hop) { xo = d.x_fanx_off[x]; xc = d.x_fanx_n[x]; }
+          list = d.fan_q;
+        }
+        for (u32 k0 = 0; k0 < c; k0 += 64) {
+          bool v = k0 + lane < c;
+          u32 q = v ? list[o + k0 + lane] : 0;
+          if (__builtin_expect(hop, 0)) hop_add(h, q, v, lane);
+          else route_emit<PASS>(d, a, p, wbase, srank, q, v, lane);
+        }
+        if (hop) {
+          const u32* xl = xt == EX_DIRECT ? d.d_x : d.fan_x;
+          for (u32 k0 = 0; k0 < xc; k0 += 64) {
+            const bool v = k0 + lane < xc;
+            hop_add(h, v ? (xl[xo + k0 + lane] | XT_EDGE) : 0u, v, lane);
           }
         }
-        // bindings are sorted by queue: a queue is emitted once, by its first hit
-        u64 hm = __ballot(hit);
-        u64 below = hm & lanemask_lt();
-        u32 qb = (u32)__shfl((int)q, below ? 63 - __clzll(below) : 0);  // nearest lower hit
-        u32 qtop = (u32)__shfl((int)q, hm ? 63 - __clzll(hm) : 0);     // highest hit
-        bool emit = hit && (below ? qb : lastq) != q;
-        route_emit<PASS>(d, a, p, wbase, srank, q, emit, lane, qo, qc);
-        if (hm) lastq = qtop;
+      } else {
+        u32 o = d.x_t_off[x], c = d.x_t_n[x];
+        u32 lastq = INVALID;
+        for (u32 k0 = 0; k0 < c; k0 += 64) {
+          bool v = k0 + lane < c;
+          u32 t = o + k0 + lane;
+          u32 q = INVALID, fl = 0, qo = INVALID, qc = INVALID;
+          bool hit = false;
+          if (v) {
+            q = d.t_queue[t];   // (a walk: or XT_EDGE | destination, the rows after the queues')
+            if (topic_cand(d, pb, p, t, fl)) {
+              // the queue's owner / consumer count load alongside the exact check's loads
+              // (a walk's row may be an edge, and route_emit loads them later: queue 0 here)
+              const u32 qi = hop ? 0u : q;
+              qo = d.world > 1 ? d.q_owner[qi] : d.my_rank;
+              qc = d.q_cons_n[qi];
+              hit = topic_verify(d, pb, p, t, fl);
+            }
+          }
+          // bindings are sorted by queue: a queue is emitted once, by its first hit
+          u64 hm = __ballot(hit);
+          u64 below = hm & lanemask_lt();
+          u32 qb = (u32)__shfl((int)q, below ? 63 - __clzll(below) : 0);  // nearest lower hit
+          u32 qtop = (u32)__shfl((int)q, hm ? 63 - __clzll(hm) : 0);     // highest hit
+          bool emit = hit && (below ? qb : lastq) != q;
+          if (__builtin_expect(hop, 0)) hop_add(h, q, emit, lane);
+          else route_emit<PASS>(d, a, p, wbase, srank, q, emit, lane, qo, qc);
+          if (hm) lastq = qtop;
+        }
       }
+      if (__builtin_expect(!hop, 1) || !hop_next(h, x, lane)) break;
+      xt = d.x_type[x] & XF_TYPE;
+    }
+    if constexpr (PASS == 0) {
+      if (hop) hop_finish(d, a, h, pb, p, srank, lane);
     }
   }
   if (PASS == 0 && lane == 0) {

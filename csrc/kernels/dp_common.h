@@ -26,6 +26,14 @@ enum : u32 {
 
 // ---- exchange types (constants.py EX_*)
 enum : u32 { EX_DIRECT = 0, EX_FANOUT = 1, EX_TOPIC = 2, EX_HEADERS = 3 };
+// ---- exchange-to-exchange bindings: x_type carries XF_HOP above the type when the exchange
+// has outgoing edges; a publish entering there walks the closure on the device (route_hop)
+enum : u32 {
+  XF_TYPE = 0xff, XF_HOP = 0x100,
+  XT_EDGE = 0x80000000u,   // t_queue of a topic row that is an edge: destination exchange slot below
+  HOP_XSLOTS = 2048,       // exchanges taking part in an edge: slot below this (one bit per slot, 32 per lane)
+  HOP_QMAX = 1024          // distinct queues a walk can reach (per-wave LDS list; enforced at bind time)
+};
 
 
 // ---- message flags

@@ -54,7 +54,8 @@ enum : u32 {
   TS_NCADEF = 68,                       // channels k_chan_advance deferred (store-record budget)
   TS_NDGET = 69,                        // Basic.Get commands the frame scan decoded (DGet list)
   TS_SPILL_USED = 70,                   // bytes of StepIn.spill_budget reserved this step (k_dequeue)
-  TS_DQ_TICKET = 71                     // k_dequeue finished-block ticket (last block: the step's runs)
+  TS_DQ_TICKET = 71,                    // k_dequeue finished-block ticket (last block: the step's runs)
+  TS_HOP_N = 72                         // hop_q entries reserved this step (exchange-to-exchange walks)
 };
 
 // Basic.Get decoded from a connection's bytes by the frame scan (no host round trip): served
@@ -148,10 +149,12 @@ struct DS {
   u16* pub_kwoff;           // [pub_max][TOPIC_WORDS] routing-key words: offset << 8 | length
   u16* pub_match;           // [pub_max][tb_pad/16]
   u32* pub_nq;
-  u32* pub_qc;              // [pub_max][8] routed queues cached by route pass 0
+  u32* pub_qc;              // [pub_max][8] routed queues cached by route pass 0 ([0] = XT_EDGE | offset
+                            // of the publish's run in hop_q: a walk that reached more than 8)
   u32* pub_slot;
   u32* pub_routed;
   u32* pub_pair_off;
+  u32* hop_q;               // [pair_max] local queue lists of this step's walks, for route pass 1
   u32* pub_slot_off;
   u32* pub_routed_rank;
   u32* pub_ret;             // 0 / 312 / 313
@@ -173,6 +176,11 @@ struct DS {
   u32* x_fan_off; u32* x_fan_n;
   u32* x_t_off; u32* x_t_n;
   u32* fan_q;               // fanout queue lists (sorted, unique)
+  // exchange-to-exchange edges (x_type bit XF_HOP: the exchange has some): destination slots
+  u32* x_fanx_off; u32* x_fanx_n;
+  u32* fan_x;               // fanout sources: destination exchanges (sorted, unique)
+  u32* d_x_off; u32* d_x_n; // [dhash] per direct key
+  u32* d_x;                 // direct sources: destination exchanges per key
   u64* d_key;               // [dhash] direct binding hash (keyhash ^ exch*K)
   i32* d_exch;              // [dhash] -1 empty
   u32* d_kb_off; u32* d_kb_len;

@@ -260,6 +260,8 @@ class Engine {
     d_.ring_pool = get("ring_pool", 1ull << 26);
     u32 fan_max = (u32)get("fan_max", 1u << 20);
     u32 dq_max = (u32)get("dq_max", 1u << 20);
+    hopx_max_ = (u32)get("hopx_max", 1u << 16);   // exchange-to-exchange edges per source type (like fan_max)
+    const u32 hopx_max = hopx_max_;
     u64 kpool = get("kpool", 16ull << 20);
     u32 nch = d_.c_max * d_.chpc;
     // pair key = queue << 1 | (source rank >= this rank) at world > 1: the pairs are
@@ -364,6 +366,7 @@ class Engine {
     d_.pub_routed = (u32*)dev("pub_routed", 4ull * d_.pub_cap);
     d_.pub_pair_off = (u32*)dev("pub_pair_off", 4ull * d_.pub_cap);
     d_.pub_slot_off = (u32*)dev("pub_slot_off", 4ull * d_.pub_cap);
+    d_.hop_q = (u32*)dev("hop_q", 4ull * d_.pair_max);
     d_.pub_routed_rank = (u32*)dev("pub_routed_rank", 4ull * d_.pub_cap);
     d_.pub_ret = (u32*)dev("pub_ret", 4ull * d_.pub_cap);
     d_.ret_list = (u32*)dev("ret_list", 4ull * d_.pub_cap);
@@ -413,6 +416,12 @@ class Engine {
     d_.x_t_off = (u32*)dev("x_t_off", 4ull * d_.x_max);
     d_.x_t_n = (u32*)dev("x_t_n", 4ull * d_.x_max);
     d_.fan_q = (u32*)dev("fan_q", 4ull * fan_max);
+    d_.x_fanx_off = (u32*)dev("x_fanx_off", 4ull * d_.x_max);
+    d_.x_fanx_n = (u32*)dev("x_fanx_n", 4ull * d_.x_max);
+    d_.fan_x = (u32*)dev("fan_x", 4ull * hopx_max);
+    d_.d_x_off = (u32*)dev("d_x_off", 4ull * dhash);
+    d_.d_x_n = (u32*)dev("d_x_n", 4ull * dhash);
+    d_.d_x = (u32*)dev("d_x", 4ull * hopx_max);
     d_.d_key = (u64*)dev("d_key", 8ull * dhash);
     d_.d_exch = (i32*)dev("d_exch", 4ull * dhash);
     d_.d_kb_off = (u32*)dev("d_kb_off", 4ull * dhash);
@@ -909,6 +918,7 @@ class Engine {
     o["chmap_size"] = d_.chmap_size; o["xhash"] = d_.xhash_mask + 1; o["dhash"] = d_.dhash_mask + 1;
     o["tb_max"] = d_.tb_max; o["tb_pad"] = d_.tb_pad; o["log_bytes"] = d_.log_bytes;
     o["spill_bytes"] = d_.spill_bytes;
+    o["hop_qmax"] = (u32)HOP_QMAX; o["hop_xslots"] = (u32)HOP_XSLOTS; o["hopx_max"] = hopx_max_;
     o["ingress_cap"] = d_.ingress_cap; o["egress_cap"] = d_.egress_cap; o["ring_pool"] = d_.ring_pool;
     o["work_cap"] = d_.work_cap; o["total_bytes"] = total_bytes_; o["req_max"] = d_.req_max;
     o["carry_budget"] = carry_budget_;
@@ -957,6 +967,7 @@ class Engine {
   int copy_mode_ = 0;      // cfg copy_engine
   bool sdma_ = true;       // copy_engine 1: NoCU copy requests
   u32 copy_wgs_ = 16;
+  u32 hopx_max_ = 1u << 16;   // capacity of fan_x / d_x (cfg hopx_max)
   int sdma_pref_ = -1, sdma_split_ = 1;
   bool gated_ = false;     // egress D2H queued at launch behind a gate (HSA SDMA)
   bool h2d_hsa_ = false;   // ingress payloads in GPU-mapped host memory go to an SDMA engine through HSA
