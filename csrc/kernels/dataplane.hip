@@ -20,334 +20,13 @@
 //   K11 refcount    body refcount + free-list / log reclamation (MessageEntity.scala:134-166)
 //
 // Every kernel reads its dynamic sizes from device counters, so grids are fixed by
-// EngineCfg and the whole step is captured once into a hipGraph (engine.cpp).
+// EngineCfg and the whole step is captured once into a hipGraph (engine.hip).
+//
+// The stages are being moved into headers dp_*.h of their own, included in pipeline order;
+// each includes the earlier headers whose functions it calls.  Moved so far: the shared
+// helpers and the frame scan; the other stages are still in this file.
 #include "dp_state.h"
-
-#define INVALID 0xffffffffu
-#define FNV64_BASIS 0xcbf29ce484222325ULL
-#define FNV64_PRIME 0x100000001b3ULL
-
-// ============================================================================ helpers
-DEV u32 lane_id() { return __lane_id(); }
-DEV u64 lanemask_lt() {
-  u32 l = __lane_id();
-  return l ? ((~0ull) >> (64 - l)) : 0ull;
-}
-DEV u32 be16(const u8* p) { return (u32(p[0]) << 8) | u32(p[1]); }
-DEV u32 be32(const u8* p) {
-  return (u32(p[0]) << 24) | (u32(p[1]) << 16) | (u32(p[2]) << 8) | u32(p[3]);
-}
-DEV u64 be64(const u8* p) { return (u64(be32(p)) << 32) | u64(be32(p + 4)); }
-DEV void wr16(u8* p, u32 v) { p[0] = u8(v >> 8); p[1] = u8(v); }
-DEV void wr32(u8* p, u32 v) { p[0] = u8(v >> 24); p[1] = u8(v >> 16); p[2] = u8(v >> 8); p[3] = u8(v); }
-DEV void wr64(u8* p, u64 v) { wr32(p, u32(v >> 32)); wr32(p + 4, u32(v)); }
-DEV u32 align16(u32 x) { return (x + 15u) & ~15u; }
-
-DEV u64 exch_hash(u32 vhost, const u8* name, u32 n) {
-  u64 h = FNV64_BASIS ^ (u64(vhost) * 0x9E3779B97F4A7C15ULL);
-  for (u32 i = 0; i < n; ++i) { h ^= name[i]; h *= FNV64_PRIME; }
-  return h;
-}
-DEV u32 fnv1a32(const u8* p, u32 n) {
-  u32 h = 0x811c9dc5u;
-  for (u32 i = 0; i < n; ++i) { h ^= p[i]; h *= 0x01000193u; }
-  return h;
-}
-
-struct __attribute__((packed, aligned(1))) U4 { u32 x, y, z, w; };
-
-// unaligned-source, unaligned-dest byte copy by the 64 lanes of one wave (kept minimal:
-// it is inlined into the store / render / pack kernels, and a batched variant with 8
-// loads in flight raised their VGPR count and cost them ~20% at 1 KB messages, measured)
-DEV void wave_copy(u8* dst, const u8* src, u32 n) {
-  u32 lane = lane_id();
-  u32 nv = n >> 4;
-  for (u32 i = lane; i < nv; i += 64) {
-    U4 v = *(const U4*)(src + (u64)i * 16);
-    *(U4*)(dst + (u64)i * 16) = v;
-  }
-  for (u32 i = (nv << 4) + lane; i < n; i += 64) dst[i] = src[i];
-}
-
-// same, by the G lanes (lane = 0..G-1) of a lane group
-template <u32 G>
-DEV void group_copy(u8* dst, const u8* src, u32 n, u32 lane) {
-  u32 nv = n >> 4;
-  for (u32 i = lane; i < nv; i += G) {
-    U4 v = *(const U4*)(src + (u64)i * 16);
-    *(U4*)(dst + (u64)i * 16) = v;
-  }
-  for (u32 i = (nv << 4) + lane; i < n; i += G) dst[i] = src[i];
-}
-
-// same, by all threads of a block
-DEV void block_copy(u8* dst, const u8* src, u32 n, u32 tid, u32 nt) {
-  u32 nv = n >> 4;
-  for (u32 i = tid; i < nv; i += nt) {
-    U4 v = *(const U4*)(src + (u64)i * 16);
-    *(U4*)(dst + (u64)i * 16) = v;
-  }
-  for (u32 i = (nv << 4) + tid; i < n; i += nt) dst[i] = src[i];
-}
-
-// Saturating reservation for counters that restart at 0 every step (control bytes,
-// delivery slots, egress budget): one atomicAdd and no give-back.  The caller owns
-// [cur, cur + want) and is granted its part below cap, so granted ranges never overlap
-// and the total granted is exactly min(sum of requests, cap) whatever the arrival order.
-// The counter itself may end above cap: every reader clamps.  (A CAS loop serialises
-// ~1000 queue blocks on one L2 line — 2.9 ms per step at 1024 fan-out queues — and an
-// add-then-give-back fast path lets a transient overshoot inflate other threads' bases.)
-DEV u32 reserve_sat(u32* p, u32 want, u32 cap, u32* base) {
-  u32 cur = want ? atomicAdd(p, want) : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  *base = cur;
-  if (cur >= cap) return 0;
-  return want < cap - cur ? want : cap - cur;
-}
-DEV u64 reserve_sat64(u64* p, u64 want, u64 cap) {
-  u64 cur = atomicAdd((unsigned long long*)p, (unsigned long long)want);
-  if (cur >= cap) return 0;
-  return want < cap - cur ? want : cap - cur;
-}
-
-// exact CAS reservation for counters that persist across steps and are also decremented
-// (per-channel delivery windows): grant min(want, cap - *p).  Contention is per channel.
-DEV u32 reserve_upto(u32* p, u32 want, u32 cap, u32* base) {
-  u32 cur = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  while (true) {
-    u32 avail = cur < cap ? cap - cur : 0;
-    u32 g = want < avail ? want : avail;
-    if (g == 0) { *base = cur; return 0; }
-    u32 prev = atomicCAS(p, cur, cur + g);
-    if (prev == cur) { *base = cur; return g; }
-    cur = prev;
-  }
-}
-
-// exclusive block scan (NT threads), returns this thread's offset; total via ref
-template <int NT>
-DEV u32 block_scan(u32 v, u32* lds, u32& total) {
-  u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  u32 x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    u32 y = __shfl_up(x, o, 64);
-    if (lane >= (u32)o) x += y;
-  }
-  if (lane == 63) lds[w] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u32 run = 0;
-    for (int i = 0; i < NT / 64; ++i) { u32 t = lds[i]; lds[i] = run; run += t; }
-    lds[NT / 64] = run;
-  }
-  __syncthreads();
-  u32 res = lds[w] + x - v;
-  total = lds[NT / 64];
-  __syncthreads();
-  return res;
-}
-
-DEV u64 shfl_xor64(u64 v, int m) {
-  return ((u64)(u32)__shfl_xor((int)(v >> 32), m, 64) << 32) | (u32)__shfl_xor((int)(u32)v, m, 64);
-}
-DEV u64 shfl64(u64 v, u32 src) {
-  u32 lo = __shfl((u32)v, src, 64), hi = __shfl((u32)(v >> 32), src, 64);
-  return (u64(hi) << 32) | lo;
-}
-DEV i64 wave_sum64(i64 v) {
-  u64 x = (u64)v;
-  for (int o = 32; o > 0; o >>= 1) {
-    u32 lo = __shfl_xor((u32)x, o, 64), hi = __shfl_xor((u32)(x >> 32), o, 64);
-    x += (u64(hi) << 32) | lo;
-  }
-  return (i64)x;
-}
-// all 64 lanes must call these (wave-uniform control flow); one atomic per distinct index
-DEV void wave_add_u32(u32* arr, u32 idx, u32 v, bool valid) {
-  u64 pend = __ballot(valid);
-  while (pend) {
-    u32 leader = __ffsll((unsigned long long)pend) - 1;
-    u32 b = __shfl(idx, leader, 64);
-    bool mine = valid && idx == b && ((pend >> lane_id()) & 1);
-    u32 x = mine ? v : 0;
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    if (lane_id() == leader) atomicAdd(&arr[b], x);
-    pend &= ~__ballot(mine);
-  }
-}
-DEV void wave_sub_u32(u32* arr, u32 idx, u32 v, bool valid) {
-  u64 pend = __ballot(valid);
-  while (pend) {
-    u32 leader = __ffsll((unsigned long long)pend) - 1;
-    u32 b = __shfl(idx, leader, 64);
-    bool mine = valid && idx == b && ((pend >> lane_id()) & 1);
-    u32 x = mine ? v : 0;
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    if (lane_id() == leader) atomicSub(&arr[b], x);
-    pend &= ~__ballot(mine);
-  }
-}
-DEV void wave_add_i64(i64* arr, u64 idx, i64 v, bool valid) {
-  u64 pend = __ballot(valid);
-  while (pend) {
-    u32 leader = __ffsll((unsigned long long)pend) - 1;
-    u64 b = shfl64(idx, leader);
-    bool mine = valid && idx == b && ((pend >> lane_id()) & 1);
-    i64 x = wave_sum64(mine ? v : 0);
-    if (lane_id() == leader) atomicAdd((unsigned long long*)&arr[b], (unsigned long long)x);
-    pend &= ~__ballot(mine);
-  }
-}
-// wave-uniform reservation of `cnt` (per lane) slots from one counter: returns lane's base
-DEV u32 wave_reserve(u32* ctr, bool want, u32* total_out = nullptr) {
-  u64 m = __ballot(want);
-  u32 n = __popcll(m);
-  u32 base = 0;
-  if (n) {
-    u32 leader = __ffsll((unsigned long long)m) - 1;
-    if (lane_id() == leader) base = atomicAdd(ctr, n);
-    base = __shfl(base, leader, 64);
-  }
-  if (total_out) *total_out = n;
-  return base + __popcll(m & lanemask_lt());
-}
-
-// a message's slot: the HBM body log, or the host spill ring for a spilled cold body
-DEV const u8* msg_slot(const DS& d, u64 log_off) {
-  return (log_off & SPILL_BIT) ? d.spill + ((log_off & ~SPILL_BIT) % d.spill_bytes) : d.log + (log_off % d.log_bytes);
-}
-
-// live-bytes accounting of a freed slot in the spill ring
-DEV void spill_free(const DS& d, u64 log_off, u32 slot_bytes) {
-  const u64 blk = ((log_off & ~SPILL_BIT) / d.log_block) % d.n_spill_blocks;
-  atomicAdd((unsigned long long*)&d.spill_live[blk], (unsigned long long)(-(i64)slot_bytes));
-}
-
-// ---- message release (K11): refcount -1, free slot + table index at zero
-DEV void release_msg(const DS& d, u32 msg) {
-  if (msg == INVALID) return;
-  i32 old = atomicSub(&d.msgs[msg].refcnt, 1);
-  if (old == 1) {
-    MsgEnt& m = d.msgs[msg];
-    if (m.log_off & COLD_BIT) {
-      atomicAdd((unsigned long long*)&d.cold_live[((m.log_off & ~COLD_BIT) >> COLD_SEG_SHIFT) % COLD_SEGS],
-                (unsigned long long)(-(i64)m.slot_bytes));
-    } else if (m.log_off & SPILL_BIT) {
-      spill_free(d, m.log_off, m.slot_bytes);
-    } else {
-      u64 blk = (m.log_off / d.log_block) % d.n_log_blocks;
-      atomicAdd((unsigned long long*)&d.log_live[blk], (unsigned long long)(-(i64)m.slot_bytes));
-      atomicAdd((unsigned long long*)d.live_bytes, (unsigned long long)(-(i64)m.slot_bytes));
-    }
-    u32 slot = atomicAdd(d.msg_free_top, 1u);
-    d.msg_free[slot] = msg;
-    atomicAdd(&d.ctr->n_freed, 1u);
-  }
-}
-
-// wave-uniform release: refcount atomics per lane, one free-list reservation and one
-// live-bytes atomic per distinct log block per wave (avoids serialising on hot words)
-DEV void wave_release(const DS& d, u32 msg, bool valid) {
-  bool freed = false, spilled = false;
-  u64 blk = 0;
-  i64 sb = 0;
-  if (valid && msg != INVALID) {
-    i32 old = atomicSub(&d.msgs[msg].refcnt, 1);
-    if (old == 1) {
-      freed = true;
-      const u64 lo = d.msgs[msg].log_off;
-      sb = d.msgs[msg].slot_bytes;
-      spilled = (lo & (SPILL_BIT | COLD_BIT)) != 0;
-      if (lo & COLD_BIT)   // (rare: bodies in the cold store)
-        atomicAdd((unsigned long long*)&d.cold_live[((lo & ~COLD_BIT) >> COLD_SEG_SHIFT) % COLD_SEGS],
-                  (unsigned long long)(-sb));
-      else if (spilled) spill_free(d, lo, (u32)sb);   // (rare: cold bodies)
-      else blk = (lo / d.log_block) % d.n_log_blocks;
-    }
-  }
-  u64 fm = __ballot(freed);
-  if (!fm) return;
-  u32 nf;
-  u32 pos = wave_reserve(d.msg_free_top, freed, &nf);
-  if (freed) d.msg_free[pos] = msg;
-  i64 tot = wave_sum64(freed && !spilled ? sb : 0);
-  if (lane_id() == __ffsll((unsigned long long)fm) - 1) {
-    atomicAdd(&d.ctr->n_freed, nf);
-    if (tot) atomicAdd((unsigned long long*)d.live_bytes, (unsigned long long)(-tot));
-  }
-  wave_add_i64(d.log_live, blk, -sb, freed && !spilled);
-}
-
-// ---- K13 snowflake ids: id = ms << 22 | worker << 12 | seq (IdGenerator.scala:14-34).
-// The reference's generator allows 4096 ids per ms per node and waits for the next ms
-// (IdGenerator.scala:55-83); one MI355X publishes ~10x that.  A GPU therefore owns
-// ID_WORKERS worker ids (group g = StepIn.worker owns g*64 .. g*64+63): 2^18 ids per ms
-// (262 M msgs/s), so the virtual position (ms << 18 | slot) never outruns the wall clock
-// and ids stay unique across restarts (the host seeds id_next above recovered ids).
-DEV u64 snowflake_id(u64 pos, u32 group) {
-  const u64 ms = pos >> ID_SLOT_BITS;
-  const u64 worker = (u64)(group & (1023 / ID_WORKERS)) * ID_WORKERS + ((pos >> 12) & (ID_WORKERS - 1));
-  return (ms << 22) | (worker << 12) | (pos & 4095);
-}
-
-// ============================================================================ topic words
-// Java String.split("\\.") semantics (QueueMatcher.scala:69-71): trailing empty
-// words dropped, "" -> [""], "..." -> [].
-struct Words { u32 eff; u32 count; };
-DEV Words words_of(const u8* s, u32 n) {
-  Words w;
-  if (n == 0) { w.eff = 0; w.count = 1; return w; }
-  u32 e = n;
-  while (e > 0 && s[e - 1] == '.') --e;
-  w.eff = e;
-  if (e == 0) { w.count = 0; return w; }
-  u32 c = 1;
-  for (u32 i = 0; i < e; ++i) c += (s[i] == '.');
-  w.count = c;
-  return w;
-}
-DEV u32 word_len(const u8* s, u32 off, u32 eff) {
-  u32 i = off;
-  while (i < eff && s[i] != '.') ++i;
-  return i - off;
-}
-DEV bool word_eq(const u8* a, u32 al, const u8* b, u32 bl) {
-  if (al != bl) return false;
-  for (u32 i = 0; i < al; ++i)
-    if (a[i] != b[i]) return false;
-  return true;
-}
-// exact topic match: '*' = one word, '#' = zero or more words (when hash_wild),
-// greedy backtracking (glob algorithm over words). Golden: models/matcher.py words_match.
-DEV bool topic_match(const u8* pat, u32 plen, const u8* key, u32 klen, bool hash_wild) {
-  Words pw = words_of(pat, plen), kw = words_of(key, klen);
-  u32 pend = pw.eff + 1, kend = kw.eff + 1;  // cursor == end -> exhausted
-  u32 p = pw.count ? 0 : pend, k = kw.count ? 0 : kend;
-  u32 sp = INVALID, sk = 0;
-  while (k < kend) {
-    u32 kl = word_len(key, k, kw.eff);
-    if (p < pend) {
-      u32 pl = word_len(pat, p, pw.eff);
-      bool is_hash = hash_wild && pl == 1 && pat[p] == '#';
-      bool is_star = pl == 1 && pat[p] == '*';
-      if (is_hash) { p += pl + 1; sp = p; sk = k; continue; }
-      if (is_star || word_eq(pat + p, pl, key + k, kl)) { p += pl + 1; k += kl + 1; continue; }
-    }
-    if (sp != INVALID) {
-      sk += word_len(key, sk, kw.eff) + 1;
-      k = sk;
-      p = sp;
-      continue;
-    }
-    return false;
-  }
-  while (p < pend) {
-    u32 pl = word_len(pat, p, pw.eff);
-    if (hash_wild && pl == 1 && pat[p] == '#') { p += pl + 1; continue; }
-    return false;
-  }
-  return true;
-}
+#include "dp_util.h"
 
 // ============================================================================ deferred control writes
 // The control plane's table writes (connection / channel / consumer state) staged while
@@ -446,7 +125,7 @@ __global__ __launch_bounds__(1024) void k_stage(DS d) {
     for (u32 k = tid; k < sizeof(Counters) / 4; k += 1024)
       if (k * 4 < offsetof(Counters, log_head)) c[k] = 0;
     if (tid == 0) {   // (per-parity scratch only: the link-ack counts and the id floor are
-                      // reset by k_marks, in the step's routing half)
+                      // reset by marks_range, in the step's routing half)
       d.ctr->n_grow = 0; d.tot[TS_NMOVE] = 0; d.tot[TS_NDEFER] = 0; d.tot[TS_TTL_BUDGET] = 0;
       d.tot[TS_NDGET] = 0;
       d.tot[TS_SPILL_USED] = 0;
@@ -475,7 +154,7 @@ __global__ __launch_bounds__(1024) void k_stage(DS d) {
   }
   u32 all_t;
   block_scan<1024>(total, lds, all_t);
-  if (tid == 0) d.tot[15] = all_t;  // work bytes used
+  if (tid == 0) d.tot[TS_WORK_USED] = all_t;
   if (all_t > d.work_cap) return;   // host sizes steps so this never triggers
   u32 run = 0;
   for (u32 b0 = 0; b0 < nseg; b0 += 1024) {
@@ -500,926 +179,7 @@ __global__ __launch_bounds__(1024) void k_stage(DS d) {
   }
 }
 
-// ============================================================================ K1 frame scan
-struct FInfo { u32 type, ch, size; bool complete, valid_hdr; };
-
-DEV FInfo frame_at(const u8* b, u32 p, u32 L, u32 fmax) {
-  FInfo f;
-  f.complete = false;
-  f.valid_hdr = false;
-  f.type = 0; f.ch = 0; f.size = 0;
-  if (p + 7 > L) return f;  // partial header
-  f.type = b[p];
-  f.ch = be16(b + p + 1);
-  f.size = be32(b + p + 3);
-  bool tok = f.type == 1 || f.type == 2 || f.type == 3 || f.type == 8;
-  bool sok = fmax == 0 || f.size + 8 <= fmax;
-  f.valid_hdr = tok && sok;
-  if (f.valid_hdr && (u64)p + 8 + f.size <= L) f.complete = (b[p + 7 + f.size] == 0xCE);
-  return f;
-}
-
-DEV i32 chan_lookup(const DS& d, u32 conn, u32 ch) {
-  const u32* m = d.chmap + (u64)conn * d.chmap_size;
-  u32 mask = d.chmap_size - 1;
-  u32 h = (ch * 0x9E3779B1u) >> 7;
-  for (u32 i = 0; i < d.chmap_size; ++i) {
-    u32 e = m[(h + i) & mask];
-    if (e == 0) return -1;
-    if ((e >> 16) == ch && (e & 0x8000u)) return (i32)(conn * d.chpc + (e & 0x7fffu));
-  }
-  return -1;
-}
-
-// candidate screen: one u16 mask per 16 work bytes; bit j set when byte j looks like a
-// frame header (type 1/2/3/8, size within the broker frame-max).  Reads 32 bytes (the
-// header of a frame starting at byte 15 ends in the next word); segments are padded
-// by >= 32 bytes in the work buffer
-// SWAR: 0x80 in every byte of v that is zero (exact per byte: no borrow between bytes)
-DEV u32 zero_bytes(u32 v) { return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu); }
-// bits 0..3 = bytes 0..3 of v hold a frame type (1, 2, 3 or 8); the multiply gathers the
-// four 0x80 flags (bits 0, 8, 16, 24 after the shift) into bits 21..24 without carries
-DEV u32 type_nibble(u32 v) {
-  const u32 h = (zero_bytes(v & 0xFCFCFCFCu) & ~zero_bytes(v)) | zero_bytes(v ^ 0x08080808u);
-  return (((h >> 7) * 0x00204081u) >> 21) & 0xFu;
-}
-DEV u32 cand_bits(uint4 A, uint4 B, u32 fm) {
-  const u32 w[6] = {A.x, A.y, A.z, A.w, B.x, B.y};
-  u32 m = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    u32 h = type_nibble(w[i]);
-    // the rare type hits: big-endian size from bytes k+3..k+6 of the 4i-byte window
-    while (h) {
-      const u32 k = __ffs(h) - 1;
-      h &= h - 1;
-      const u32 v = k == 0 ? __builtin_amdgcn_alignbyte(w[i + 1], w[i], 3)
-                           : __builtin_amdgcn_alignbyte(w[i + 2], w[i + 1], k - 1);
-      const u32 sz = __builtin_bswap32(v);
-      if (fm == 0 || sz <= fm - 8) m |= 1u << (4 * i + k);
-    }
-  }
-  return m;
-}
-DEV u32 cand_word(const u8* w16, u32 fm) {
-  const uint4* q = (const uint4*)w16;
-  return cand_bits(q[0], q[1], fm);
-}
-
-#define FS_MARK(k) \
-  do { if (tid == 0 && d.dbg) d.dbg[(u64)s * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-constexpr u32 FS_AM_MAX = 8192;  // 128 KB segment; 16 KB of LDS
-// Segments up to FS_STAGE bytes (the screen's 32-byte read-ahead included) are copied
-// into LDS by the screen pass itself, and every later phase reads the segment's bytes
-// from LDS instead of HBM (frame headers, method ids, body sizes, control bytes: ~15
-// dependent global round trips per segment before).  The block's LDS is one pool carved
-// per segment: staged segments hold up to FS_CAND_STAGED candidates next to the 72 KB
-// stage, other segments CAND_MAX candidates (a 128 KB segment of 1-byte messages)
-constexpr u32 FS_STAGE = 72u << 10;
-constexpr u32 FS_CAND_STAGED = 6144;
-// candidate arrays: wend + cpos (u32), chain / screen mask (u16), csucc (i16), claim (u8)
-constexpr u32 fs_cand_bytes(u32 cmax, u32 amw) { return cmax * 4 * 2 + (cmax > amw ? cmax : amw) * 2 + cmax * 2 + cmax; }
-constexpr u32 FS_POOL_STAGED = FS_STAGE + fs_cand_bytes(FS_CAND_STAGED, FS_STAGE / 16);
-constexpr u32 FS_POOL_FULL = fs_cand_bytes(CAND_MAX, FS_AM_MAX);
-constexpr u32 FS_POOL = ((FS_POOL_STAGED > FS_POOL_FULL ? FS_POOL_STAGED : FS_POOL_FULL) + 15) & ~15u;
-static_assert(FS_POOL <= 156u << 10, "k_frame_scan LDS pool");
-// one block of FS_NT threads per segment: 16 waves (4 per SIMD) hide the screen's
-// dependent integer chains, which one wave per SIMD could not
-#define FS_NT 1024
-// a content publish whose whole command (method + header + body frames) cannot fit the
-// connection's carry: the host assembles it (FE_CTRL of its method + header frames; the
-// body is read on the host and enqueued as an MF_HOSTPUB record)
-DEV bool big_publish(const DS& d, u32 msize, u32 hsize, u64 bsz, u32 fmax) {
-  const u64 fb = fmax > 8 ? fmax - 8 : 0;
-  const u64 nb = bsz == 0 ? 0 : (fb ? (bsz + fb - 1) / fb : 1);
-  return (u64)msize + 8 + hsize + 8 + bsz + 8 * nb > d.carry_cap;
-}
-
-// bytes [sh, sh + 16) of the 32 bytes a:b (sh 0..15): a two-level word barrel shift (by 2
-// words, then 1 -- named registers and selects: an indexed word array here was lowered to
-// a scratch-memory table, 48 bytes per lane), then four dword funnel shifts
-DEV uint4 shift_pair(uint4 a, uint4 b, u32 sh) {
-  const u32 q = sh >> 2, r = sh & 3;
-  const bool q2 = (q & 2) != 0, q1 = (q & 1) != 0;
-  const u32 s0 = q2 ? a.z : a.x, s1 = q2 ? a.w : a.y, s2 = q2 ? b.x : a.z;
-  const u32 s3 = q2 ? b.y : a.w, s4 = q2 ? b.z : b.x, s5 = q2 ? b.w : b.y;
-  const u32 w0 = q1 ? s1 : s0, w1 = q1 ? s2 : s1, w2 = q1 ? s3 : s2, w3 = q1 ? s4 : s3, w4 = q1 ? s5 : s4;
-  if (!r) return make_uint4(w0, w1, w2, w3);
-  return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, r), __builtin_amdgcn_alignbyte(w2, w1, r),
-                    __builtin_amdgcn_alignbyte(w3, w2, r), __builtin_amdgcn_alignbyte(w4, w3, r));
-}
-// word c (bytes [16c, 16c + 16)) of a segment = the connection's carry (cl bytes, C
-// 16-aligned) then its new ingress bytes (N 16-aligned; reading up to 32 bytes past them
-// stays inside the ingress slot's slack); bytes past the segment are don't-care
-DEV uint4 seg_word(const u8* C, u32 cl, const u8* N, u32 c) {
-  const u32 b0 = c * 16;
-  if (b0 + 16 <= cl) return *(const uint4*)(C + b0);
-  if (b0 >= cl) {
-    const u32 o = b0 - cl, k = o >> 4, sh = o & 15;
-    const uint4 a = ((const uint4*)N)[k];
-    return sh ? shift_pair(a, ((const uint4*)N)[k + 1], sh) : a;
-  }
-  u32 v[4] = {0, 0, 0, 0};   // the word holding the carry's end and the new bytes' start
-#pragma unroll
-  for (u32 j = 0; j < 16; ++j) {
-    const u32 i = b0 + j;
-    const u32 x = i < cl ? C[i] : N[i - cl];
-    v[j >> 2] |= x << (8 * (j & 3));
-  }
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-// Basic.Get the step can serve itself: a named queue of the connection's vhost (the default
-// exchange's direct binding of that name), owned by this rank, not another connection's
-// exclusive queue.  An empty name (the channel's last declared queue) and every error case
-// go to the host.  Method args at b + p + 7: class, method, ticket, queue shortstr, bits.
-DEV bool dget_resolve(const DS& d, u32 conn, const u8* b, u32 p, u32 size, u32& q, u32& noack) {
-  if (size < 8) return false;
-  const u32 a = p + 7 + 6, n = b[a], end = p + 7 + size;
-  if (n == 0 || a + 1 + n + 1 > end) return false;
-  const u8* name = b + a + 1;
-  const u32 vh = d.conn_vhost[conn];
-  const u64 hk = exch_hash(vh, name, 0);   // the vhost's default exchange ("")
-  i32 xs = -1;
-  for (u32 j = 0; j <= d.xhash_mask; ++j) {
-    const u32 slot = (u32)(hk + j) & d.xhash_mask;
-    const i32 v = d.x_hval[slot];
-    if (v < 0) break;
-    if (d.x_hkey[slot] == hk) { xs = v; break; }
-  }
-  if (xs < 0 || d.x_type[xs] != EX_DIRECT) return false;
-  const u64 k = fnv1a64_dev(name, n) ^ (u64(xs) * 0x9E3779B97F4A7C15ULL);
-  for (u32 j = 0; j <= d.dhash_mask; ++j) {
-    const u32 s = (u32)(k + j) & d.dhash_mask;
-    const i32 ex = d.d_exch[s];
-    if (ex < 0) return false;
-    if (ex == xs && d.d_key[s] == k && word_eq(d.kpool + d.d_kb_off[s], d.d_kb_len[s], name, n)) {
-      if (d.d_q_n[s] != 1) return false;
-      const u32 qq = d.d_q[d.d_q_off[s]];
-      const u32 ex_owner = d.q_excl[qq];
-      if (!d.q_active[qq] || d.q_owner[qq] != d.my_rank || (ex_owner && ex_owner != conn + 1)) return false;
-      q = qq;
-      noack = b[a + 1 + n] & 1u;
-      return true;
-    }
-  }
-  return false;
-}
-
-DEV void frame_scan_seg(const DS& d, const u32 s) {
-  __shared__ uint4 fs_pool[FS_POOL / 16];
-  __shared__ u32 sc[FS_NT / 64 + 1];
-  __shared__ u32 sh_m, sh_over, sh_ok, sh_nf, sh_stop, sh_brk;
-  __shared__ u32 sh_cmd_base, sh_frag_base, sh_ncmd;
-  __shared__ u32 sh_get0, sh_gch, sh_gq, sh_gna, sh_gbase;   // Basic.Get: the segment's first, its key
-  __shared__ u32 sh_split;   // split mode: bytes [0, sh_split) are in the work buffer
-
-  const u32 tid = threadIdx.x;
-  const u32 conn = d.segs[s].conn;
-  const u32 L = d.seg_total[s];
-  const u32 seg_len = d.segs[s].len, seg_cl = L - seg_len, src = d.segs[s].src;
-  // the step's new bytes are read where their H2D put them: the ingress slots follow the
-  // work buffers in one allocation, so a u32 offset from d.work reaches them, and every
-  // later reader (decode, route-store, returns, gets) takes a frame's bytes from there.  A
-  // segment with no carry is scanned in place (nothing goes to the work buffer); one with a
-  // carry is staged in LDS by the screen and only its head -- the carry and the frame that
-  // straddles into the new bytes -- is written to the work buffer (split mode, OFF below):
-  // the work copy of the step's bytes is gone.  Single GPU (sharded steps read imports
-  // beside the work buffer).
-  const u64 ing_rel = (u64)d.in->ingress - (u64)d.work;
-  const bool ing_ok = d.scan_inplace && d.world == 1 && (u64)d.in->ingress > (u64)d.work && ing_rel + src + L + 64 < (1ull << 32) &&
-                      d.tot[15] <= d.work_cap;
-  const bool inplace = ing_ok && seg_cl == 0 && L > 0;
-  const u32 wbase = inplace ? (u32)(ing_rel + src) : d.seg_start[s];
-  const u8* const bg = d.work + wbase;   // the segment in HBM: the work buffer or its ingress slot
-  const u8* b = bg;                      // switched to the LDS stage after the screen
-  // the pool for this segment: [stage] wend cpos chain/amask csucc claim
-  const u32 nm16 = (L + 15) >> 4;
-  const bool staged = nm16 * 16 + 32 <= FS_STAGE;
-  const u32 cmax = staged ? FS_CAND_STAGED : CAND_MAX;
-  u8* const pool = (u8*)fs_pool;
-  uint4* const fs_stage = fs_pool;
-  // per accepted candidate: its frame end | complete << 31 (phase b reuses it instead of
-  // re-reading the header); ~0u = recompute
-  u32* const wend = (u32*)(pool + (staged ? FS_STAGE : 0u));
-  u32* const cpos = wend + cmax;
-  // chain (first written in phase c) aliases amask (used only in phase a, which ends on a
-  // __syncthreads)
-  u16* const chain_am = (u16*)(cpos + cmax);
-  u16* const chain = chain_am;
-  u16* const amask = chain_am;
-  int16_t* const csucc = (int16_t*)(chain_am + (staged ? FS_CAND_STAGED : (CAND_MAX > FS_AM_MAX ? CAND_MAX : FS_AM_MAX)));
-  u8* const claim = (u8*)(csucc + cmax);
-  const u32 fmax = d.conn_frame_max[conn];
-  FS_MARK(15);
-  const u8* const seg_C = d.carry + (u64)conn * d.carry_cap;
-  const u8* const seg_N = (const u8*)d.in->ingress + d.segs[s].src;
-  // the common segment is copied into the work buffer by the screen pass itself: one read
-  // of the sources, the work copy, the LDS stage and the candidate mask from the same
-  // registers (was: a copy pass, then the screen re-reading the copy)
-  const bool fit = d.tot[15] <= d.work_cap;
-  const bool fuse = fit && !inplace && L > 0 && ((L + 15) >> 4) <= FS_AM_MAX && !d.conn_paused[conn];
-  const bool split = fuse && staged && ing_ok;   // (the screen then leaves the work buffer alone)
-  if (fit && !fuse && !inplace) {
-    // the segment into the work buffer (fused k_stage copy): the connection's carry, then
-    // its new ingress bytes.  k_decode / k_route_store read publishes from there
-    u8* const dst = d.work + wbase;
-    if (seg_cl) block_copy(dst, seg_C, seg_cl, tid, FS_NT);
-    if (seg_len) block_copy(dst + seg_cl, seg_N, seg_len, tid, FS_NT);
-  }
-  __threadfence_block();
-  __syncthreads();
-  SegOut so;
-  so.conn = conn; so.status = 0; so.consumed = 0; so.carry = L; so.ncmds = 0; so.err_off = 0;
-  so.pad[0] = so.pad[1] = 0;
-
-  if (d.conn_paused[conn]) {
-    // hold everything; write carry back (k_stage already appended new bytes)
-    if (L > d.carry_cap) { so.status = SS_TOO_LARGE; so.carry = 0; }
-    else block_copy(d.carry + (u64)conn * d.carry_cap, b, L, tid, FS_NT);
-    if (tid == 0) {
-      so.status |= SS_PAUSED;
-      d.carry_len[conn] = so.carry;
-      d.seg_out[s] = so;
-      d.seg_cmd_base[s] = INVALID;
-      d.seg_npub[s] = 0;
-      d.seg_nack[s] = 0;
-    }
-    return;
-  }
-  if (L == 0) {
-    if (tid == 0) {
-      d.carry_len[conn] = 0; d.seg_out[s] = so; d.seg_cmd_base[s] = INVALID; d.seg_npub[s] = 0; d.seg_nack[s] = 0;
-    }
-    return;
-  }
-  if (tid == 0) { sh_m = 0; sh_over = 0; }
-  __syncthreads();
-
-  FS_MARK(0);
-  // ---- (a) candidates: screen the segment (one mask bit per byte that looks like a frame
-  // header), validate them against the connection's frame-max / end marker, append the
-  // trailing positions that can only hold a partial header.  cpos = accepted positions in
-  // order; wend[i] = candidate i's frame end | complete << 31 (~0u: phase b re-reads it)
-  {
-    const u32 nm = (L + 15) >> 4;
-    const u32 per = (nm + FS_NT - 1) / FS_NT;
-    const u32 c0 = tid * per;
-    const u32 c1 = c0 + per < nm ? c0 + per : nm;
-    const u32 lim = L >= 7 ? L - 6 : 0;   // full-header positions are p < lim
-    const bool use_am = nm <= FS_AM_MAX;
-    const u32 fmg = d.frame_max_global;
-    if (use_am) {   // candidate screen of the segment into LDS (fused k_cand), coalesced reads
-      const uint4* W = (const uint4*)bg;   // 16-aligned; >= 32 bytes of padding after the segment
-      uint4* const WD = (uint4*)(d.work + wbase);
-      // every word is read from memory once: a lane's next word (the screen looks 16 bytes
-      // ahead) is its neighbour lane's word, the wave's last lane reads it itself -- all 256
-      // segment blocks screen at once, so the double read made this phase HBM-bound
-      const u32 ln = lane_id();
-      // (wave-uniform trip count: every lane of a wave takes part in the shuffles)
-      for (u32 cb = tid - ln; cb < nm; cb += FS_NT * 4) {
-        const u32 cc = cb + ln;
-        uint4 x[4], y[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {   // every load of the batch in flight before any use
-          const u32 c = cc + k * FS_NT;   // (c == nm: the word after the segment, read as slack)
-          x[k] = make_uint4(0, 0, 0, 0);
-          y[k] = make_uint4(0, 0, 0, 0);
-          if (c <= nm) x[k] = fuse ? seg_word(seg_C, seg_cl, seg_N, c) : W[c];
-          if (ln == 63 && c < nm) y[k] = fuse ? seg_word(seg_C, seg_cl, seg_N, c + 1) : W[c + 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint4 nx = make_uint4(__shfl_down(x[k].x, 1), __shfl_down(x[k].y, 1), __shfl_down(x[k].z, 1),
-                                      __shfl_down(x[k].w, 1));
-          if (ln != 63) y[k] = nx;
-          const u32 c = cc + k * FS_NT;
-          if (c < nm) {
-            amask[c] = (u16)cand_bits(x[k], y[k], fmg);
-            if (staged) fs_stage[c] = x[k];
-            if (fuse && !split) WD[c] = x[k];
-          }
-        }
-      }
-      if (fuse && !staged) __threadfence_block();   // the later phases read the work copy
-      if (staged && tid < 2) fs_stage[nm + tid] = make_uint4(0, 0, 0, 0);   // the screen's read-ahead
-      __syncthreads();
-      if (staged) b = (const u8*)fs_stage;
-    }
-    FS_MARK(12);
-    // raw candidates per thread (its words are contiguous: the scan keeps position order)
-    u32 rc = 0;
-    if (use_am)
-      for (u32 c = c0; c < c1; ++c) {
-        u32 mk = amask[c];
-        if (c * 16 + 16 > lim) mk &= lim > c * 16 ? (1u << (lim - c * 16)) - 1u : 0u;
-        rc += __popc(mk);
-      }
-    u32 rtot;
-    u32 roff = block_scan<FS_NT>(rc, sc, rtot);
-    FS_MARK(13);
-    u32 tot = 0;
-    if (use_am && rtot <= cmax) {
-      // every raw candidate validated in parallel (one thread each), then compacted in
-      // place chunk by chunk: accepted entries only move left, after the chunk was read
-      for (u32 c = c0; c < c1; ++c) {
-        u32 mk = amask[c];
-        while (mk) {
-          const u32 j = __ffs(mk) - 1;
-          mk &= mk - 1;
-          const u32 p = c * 16 + j;
-          if (p >= lim) break;
-          cpos[roff++] = p;
-        }
-      }
-      __syncthreads();
-      FS_MARK(14);
-      for (u32 k0 = 0; k0 < rtot; k0 += FS_NT) {
-        const u32 i = k0 + tid;
-        bool ok = false;
-        u32 p = 0, we = ~0u;
-        if (i < rtot) {
-          p = cpos[i];
-          const FInfo f = frame_at(b, p, L, fmax);
-          ok = f.valid_hdr && (f.complete || (u64)p + 8 + f.size > L);
-          const u64 e64 = (u64)p + 8 + f.size;
-          we = e64 < 0x7fffffffull ? ((f.complete ? 0x80000000u : 0u) | (u32)e64) : ~0u;
-        }
-        u32 all;
-        const u32 o = block_scan<FS_NT>(ok ? 1u : 0u, sc, all);
-        if (ok) { cpos[tot + o] = p; wend[tot + o] = we; }
-        tot += all;
-      }
-    } else {
-      // very long segment (no LDS mask) or more raw candidates than cmax: each
-      // thread validates its own words, twice (count, then emit)
-      u32 cnt = 0;
-      for (u32 c = c0; c < c1; ++c) {
-        u32 mk = use_am ? (u32)amask[c] : cand_word(b + c * 16, fmg);
-        u32 acc = 0;
-        while (mk) {
-          u32 j = __ffs(mk) - 1;
-          mk &= mk - 1;
-          u32 p = c * 16 + j;
-          if (p >= lim) break;
-          FInfo f = frame_at(b, p, L, fmax);
-          if (f.valid_hdr && (f.complete || (u64)p + 8 + f.size > L)) { ++cnt; acc |= 1u << j; }
-        }
-        if (use_am) amask[c] = (u16)acc;
-      }
-      u32 off = block_scan<FS_NT>(cnt, sc, tot);
-      for (u32 c = c0; c < c1; ++c) {
-        u32 mk = use_am ? (u32)amask[c] : cand_word(b + c * 16, fmg);
-        while (mk) {
-          u32 j = __ffs(mk) - 1;
-          mk &= mk - 1;
-          u32 p = c * 16 + j;
-          if (p >= lim) break;
-          bool acc = use_am;
-          if (!use_am) {
-            FInfo f = frame_at(b, p, L, fmax);
-            acc = f.valid_hdr && (f.complete || (u64)p + 8 + f.size > L);
-          }
-          if (acc) {
-            if (off < cmax) { cpos[off] = p; wend[off] = ~0u; }
-            ++off;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      u32 nmc = tot;
-      for (u32 p = lim; p < L; ++p) {
-        if (nmc < cmax) { cpos[nmc] = p; wend[nmc] = ~0u; }
-        ++nmc;
-      }
-      if (nmc > cmax) { sh_over = 1; nmc = cmax; }
-      sh_m = nmc;
-    }
-    __syncthreads();
-  }
-  FS_MARK(1);
-  const u32 m = sh_m;
-  const bool over = sh_over != 0;
-
-  // ---- (b) successor of every candidate (-1 exact end, -2 partial/unknown, -3 broken)
-  for (u32 i = tid; i < m; i += FS_NT) {
-    u32 p = cpos[i];
-    bool complete;
-    u32 e;
-    const u32 we = wend[i];
-    if (we != ~0u) {
-      complete = (we >> 31) != 0;
-      e = we & 0x7fffffffu;
-    } else {
-      FInfo f = frame_at(b, p, L, fmax);
-      complete = f.complete;
-      e = p + 8 + f.size;
-    }
-    i32 sx;
-    if (!complete) sx = -2;
-    else {
-      if (e == L) sx = -1;
-      else {
-        u32 lo = i + 1, hi = m;  // successor lies strictly after i
-        while (lo < hi) { u32 mid = (lo + hi) >> 1; if (cpos[mid] < e) lo = mid + 1; else hi = mid; }
-        if (lo < m && cpos[lo] == e) sx = (i32)lo;
-        else sx = (over && e > cpos[m - 1]) ? -2 : -3;
-      }
-    }
-    csucc[i] = (int16_t)sx;
-  }
-  FS_MARK(2);
-  // ---- (c) chain.  A failure is a candidate whose successor is not the next candidate;
-  // between failures the chain runs through consecutive candidates.  The failures are
-  // compacted in order (into wend, dead after (b)), then one thread walks failure to
-  // failure -- one step per jump over false candidates (e.g. timestamp bytes inside a
-  // header that look like a frame running past the segment end), not one per frame --
-  // recording runs, which all threads expand into chain[].  A single run starting at 0
-  // is the implicit chain (frame f = candidate f)
-  constexpr u32 FS_RUNS = 1024;            // run records at the top of wend
-  const u32 FS_FAIL_MAX = cmax - 2 * FS_RUNS;
-  __syncthreads();   // csucc / wend of (b) complete
-  FS_MARK(9);
-  {
-    const u32 per = (m + FS_NT - 1) / FS_NT;
-    const u32 i0 = tid * per < m ? tid * per : m;
-    const u32 i1 = i0 + per < m ? i0 + per : m;
-    u32 nfl = 0;
-    for (u32 i = i0; i < i1; ++i) nfl += csucc[i] != (i32)(i + 1);
-    u32 tfl;
-    u32 o = block_scan<FS_NT>(nfl, sc, tfl);
-    for (u32 i = i0; i < i1; ++i)
-      if (csucc[i] != (i32)(i + 1) && o < FS_FAIL_MAX) wend[o++] = i;
-    __syncthreads();
-    // per failure x (candidate F[x] = wend[x]) with a successor: the first failure at or
-    // after that successor, in parallel (binary search over F); kept in chain[] (free
-    // until the expansion below), 0xFFFF = the chain ends at this failure
-    if (tfl <= FS_FAIL_MAX)
-      for (u32 x = tid; x < tfl; x += FS_NT) {
-        const i32 sx = csucc[wend[x]];
-        u32 nx = 0xFFFFu;
-        if (sx >= 0) {
-          u32 lo = x + 1, hi = tfl;   // successors lie after the failure
-          while (lo < hi) { u32 mid = (lo + hi) >> 1; if (wend[mid] < (u32)sx) lo = mid + 1; else hi = mid; }
-          nx = lo;   // < tfl: the last candidate is a failure
-        }
-        chain[x] = (u16)nx;
-      }
-    __syncthreads();
-    FS_MARK(10);
-    if (tid == 0) {
-      u32 nf = 0, brk = 0, nrun = 0;
-      if (m == 0 || cpos[0] != 0) {
-        brk = 1;  // first bytes are not a frame header
-      } else if (tfl <= FS_FAIL_MAX) {
-        // failure to failure: the run [i, F[x]], then the run from F[x]'s successor
-        u32 i = 0, x = 0;
-        while (true) {
-          const u32 k = wend[x], nx = chain[x];
-          if (nrun < FS_RUNS) { wend[FS_FAIL_MAX + 2 * nrun] = i; wend[FS_FAIL_MAX + 2 * nrun + 1] = nf; }
-          ++nrun;
-          nf += k - i + 1;
-          if (nx == 0xFFFFu) { brk = csucc[k] == -3; break; }
-          i = (u32)csucc[k];
-          x = nx;
-        }
-      }
-      if (m != 0 && cpos[0] == 0 && (tfl > FS_FAIL_MAX || nrun > FS_RUNS)) {
-        nf = 0; brk = 0; nrun = FS_RUNS + 1;   // pathological: serial walk
-        i32 i = 0;
-        while (true) {
-          chain[nf++] = (u16)i;
-          i32 sx = csucc[i];
-          if (sx >= 0) { i = sx; continue; }
-          if (sx == -3) brk = 1;
-          break;
-        }
-      }
-      sh_nf = nf;
-      sh_brk = brk;
-      sh_ok = nrun;
-    }
-    __syncthreads();
-    FS_MARK(11);
-    const u32 nrun = sh_ok;
-    if (nrun > 1 && nrun <= FS_RUNS) {
-      for (u32 r = tid; r < nrun; r += FS_NT) {
-        const u32 ci = wend[FS_FAIL_MAX + 2 * r], f0 = wend[FS_FAIL_MAX + 2 * r + 1];
-        const u32 f1 = r + 1 < nrun ? wend[FS_FAIL_MAX + 2 * r + 3] : sh_nf;
-        for (u32 f = f0; f < f1; ++f) chain[f] = (u16)(ci + (f - f0));
-      }
-    }
-    __syncthreads();
-  }
-  FS_MARK(3);
-  const u32 nf = sh_nf;
-  const bool implicit_chain = sh_ok == 1;
-#define CPOS(f) (cpos[implicit_chain ? (f) : chain[f]])
-
-  // ---- (d) commands: each method frame walks its content frames
-  for (u32 f = tid; f < nf; f += FS_NT) claim[f] = 0;
-  if (tid == 0) { sh_stop = (nf << 3) | 7; sh_get0 = INVALID; }  // (frame << 3) | reason; 7 = none
-  __syncthreads();
-  // stop reasons: 0 = after control, 1 = incomplete, 2 = unexpected frame, 3 = frame error,
-  // 4 = before a command that may not follow the segment's Basic.Gets in one step
-  for (u32 f = tid; f < nf; f += FS_NT) {
-    u32 p = CPOS(f);
-    FInfo fi = frame_at(b, p, L, fmax);
-    if (!fi.complete) {
-      if (fi.type == 1 || fi.type == 8 || !fi.valid_hdr) atomicMin(&sh_stop, (f << 3) | 1);
-      continue;
-    }
-    if (fi.type == 8) { claim[f] = 1; continue; }
-    if (fi.type != 1) continue;
-    claim[f] = 1;
-    if (fi.size < 4) { atomicMin(&sh_stop, (f << 3) | 3); continue; }
-    u32 cls = be16(b + p + 7), mid = be16(b + p + 9);
-    bool content = (cls == 60 && mid == 40);
-    bool data = (cls == 60 && (mid == 40 || mid == 80 || mid == 90 || mid == 120)) && fi.ch != 0 &&
-                chan_lookup(d, conn, fi.ch) >= 0;
-    if (cls == 60 && mid == 70 && fi.ch != 0 && chan_lookup(d, conn, fi.ch) >= 0) {
-      u32 gq, gna;
-      if (dget_resolve(d, conn, b, p, fi.size, gq, gna)) { atomicMin(&sh_get0, f); continue; }
-    }
-    if (!content) {
-      if (!data) atomicMin(&sh_stop, ((f + 1) << 3) | 0);
-      continue;
-    }
-    // header then bodies on the same channel
-    u32 g = f + 1;
-    if (g >= nf) { atomicMin(&sh_stop, (f << 3) | 1); continue; }
-    u32 hp = CPOS(g);
-    FInfo hi = frame_at(b, hp, L, fmax);
-    if (!hi.complete) { atomicMin(&sh_stop, (f << 3) | 1); continue; }
-    if (hi.type != 2 || hi.ch != fi.ch || hi.size < 14) { atomicMin(&sh_stop, (f << 3) | 2); continue; }
-    claim[g] = 1;
-    u64 bsz = be64(b + hp + 7 + 4);
-    if (data && big_publish(d, fi.size, hi.size, bsz, fmax)) {   // host-assembled: stop after its header
-      atomicMin(&sh_stop, ((g + 1) << 3) | 0);
-      continue;
-    }
-    u64 got = 0;
-    u32 e = g;
-    bool bad = false, incomplete = false;
-    while (got < bsz) {
-      ++e;
-      if (e >= nf) { incomplete = true; break; }
-      u32 bp = CPOS(e);
-      FInfo bi = frame_at(b, bp, L, fmax);
-      if (!bi.complete) { incomplete = true; break; }
-      if (bi.type != 3 || bi.ch != fi.ch) { atomicMin(&sh_stop, (f << 3) | 2); bad = true; break; }
-      claim[e] = 1;
-      got += bi.size;
-      if (got > bsz) { atomicMin(&sh_stop, (f << 3) | 3); bad = true; break; }
-    }
-    if (incomplete) atomicMin(&sh_stop, (f << 3) | 1);
-    (void)bad;
-    if (!data) atomicMin(&sh_stop, ((e + 1) << 3) | 0);
-  }
-  __syncthreads();
-  for (u32 f = tid; f < nf; f += FS_NT) {
-    if (claim[f]) continue;
-    FInfo fi = frame_at(b, CPOS(f), L, fmax);
-    if (fi.complete) atomicMin(&sh_stop, (f << 3) | 2);
-  }
-  __syncthreads();
-  if (sh_get0 != INVALID) {   // (block-uniform) the segment serves Basic.Gets in this step
-    // they all ask the same (channel, queue, no-ack) -- any two then answer alike, whichever
-    // is served first -- and nothing but such Gets follows the first in this step (an ack
-    // after a Get may name its delivery tag, which the step assigns later); the rest of the
-    // segment waits in the carry for the next step
-    const u32 g0 = sh_get0;
-    if (tid == g0 % FS_NT) {
-      const u32 p = CPOS(g0);
-      FInfo fi = frame_at(b, p, L, fmax);
-      u32 gq = 0, gna = 0;
-      dget_resolve(d, conn, b, p, fi.size, gq, gna);
-      sh_gch = fi.ch; sh_gq = gq; sh_gna = gna;
-    }
-    __syncthreads();
-    for (u32 f = g0 + 1 + tid; f < nf; f += FS_NT) {
-      const u32 p = CPOS(f);
-      if (b[p] != 1) continue;   // content and heartbeat frames go with their method / nothing
-      FInfo fi = frame_at(b, p, L, fmax);
-      bool same = false;
-      if (fi.complete && fi.size >= 4 && be16(b + p + 7) == 60 && be16(b + p + 9) == 70 && fi.ch == sh_gch) {
-        u32 gq, gna;
-        same = dget_resolve(d, conn, b, p, fi.size, gq, gna) && gq == sh_gq && gna == sh_gna;
-      }
-      if (!same) atomicMin(&sh_stop, (f << 3) | 4);
-    }
-    __syncthreads();
-  }
-  FS_MARK(4);
-  u32 stop = sh_stop;
-  u32 kf = stop >> 3, reason = stop & 7;
-  if (kf > nf) kf = nf;
-  if (reason == 7 && sh_brk) { reason = 3; }  // chain ended on a broken frame
-
-  // consumed bytes: up to frame kf (or the end of the chain)
-  u32 consumed;
-  if (kf < nf) consumed = CPOS(kf);
-  else if (nf == 0) consumed = 0;
-  else {
-    u32 lp = CPOS(nf - 1);
-    FInfo lf = frame_at(b, lp, L, fmax);
-    consumed = lf.complete ? lp + 8 + lf.size : lp;
-  }
-  if (reason == 3 || reason == 2) {
-    so.status |= (reason == 3) ? SS_FRAME_ERROR : SS_UNEXPECTED;
-    so.err_off = consumed;
-  }
-  if (over && reason != 0 && kf == nf) so.status |= SS_OVERFLOW;
-  if (reason == 4) so.status |= SS_OVERFLOW;   // the carry is re-presented to the next step
-
-  // split mode: the work buffer gets the carry and the frame that runs from it into the new
-  // bytes (frames start inside the carry only before that point); later frames are read from
-  // the ingress slot
-  if (split) {
-    if (tid == 0) sh_split = seg_cl;
-    __syncthreads();
-    for (u32 f = tid; f < nf; f += FS_NT) {
-      const u32 p = CPOS(f);
-      if (p >= seg_cl) continue;
-      const FInfo fi = frame_at(b, p, L, fmax);
-      const u64 e = fi.complete ? (u64)p + 8 + fi.size : (u64)L;
-      atomicMax(&sh_split, (u32)(e < L ? e : L));
-    }
-    __syncthreads();
-    uint4* const WD = (uint4*)(d.work + wbase);
-    const u32 nw = (sh_split + 15) >> 4;
-    for (u32 w = tid; w < nw; w += FS_NT) WD[w] = fs_stage[w];
-    __syncthreads();
-  }
-  const u32 sp = split ? sh_split : inplace ? 0u : L + 1u;
-  // a frame's offset from d.work (frames lie wholly below sp or at / above it)
-  auto OFF = [&](u32 pos) -> u32 { return pos < sp ? wbase + pos : (u32)(ing_rel + src + pos - seg_cl); };
-  FS_MARK(5);
-  // ---- (e) emit commands for method frames < kf
-  u32 run = 0, frun = 0;
-  if (tid == 0) { sh_cmd_base = INVALID; sh_ncmd = 0; }
-  __syncthreads();
-  // count first -- unless the commands fit one emit chunk (the common case): then the emit
-  // pass reserves them itself, from the scans it runs anyway
-  const bool one = kf <= FS_NT;   // (block-uniform)
-  u32 my_cmds = 0, my_frags = 0;
-  for (u32 f = tid; f < kf && !one; f += FS_NT) {
-    u32 p = CPOS(f);
-    if (b[p] != 1) continue;
-    ++my_cmds;
-    if (be16(b + p + 7) == 60 && be16(b + p + 9) == 40) {
-      // frags: frames after header until the next method
-      u32 e = f + 2;
-      while (e < kf && b[CPOS(e)] == 3) { ++my_frags; ++e; }
-    }
-  }
-  u32 tc = 0, tfr = 0;
-  if (!one) {
-    block_scan<FS_NT>(my_cmds, sc, tc);
-    block_scan<FS_NT>(my_frags, sc, tfr);
-  }
-  // one uncontended atomicAdd per block (a CAS loop here serialises all blocks);
-  // on overflow the reserved in-range slots are filled with CK_NONE and the whole
-  // segment is carried to the next step
-  if (!one && tid == 0) {
-    u32 cb = tc ? atomicAdd(&d.ctr->n_cmds, tc) : 0;
-    u32 fb = tfr ? atomicAdd(&d.ctr->n_frags, tfr) : 0;
-    sh_frag_base = fb;
-    sh_cmd_base = cb;
-    sh_ncmd = (cb + tc > d.cmd_max || fb + tfr > d.frag_max) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (sh_ncmd && tc > 0) {
-    u32 cb = sh_cmd_base;
-    for (u32 i = cb + tid; i < cb + tc && i < d.cmd_max; i += FS_NT) {
-      d.cmds[i].kind = CK_NONE;
-      d.cmd_is_pub[i] = 0;
-      d.cmd_is_ack[i] = 0;
-    }
-    if (tid == 0) sh_cmd_base = INVALID;
-    __syncthreads();
-  }
-  if (sh_cmd_base == INVALID && tc > 0) {
-    so.status |= SS_OVERFLOW;
-    so.status &= ~(SS_FRAME_ERROR | SS_UNEXPECTED);
-    consumed = 0;
-    kf = 0;
-    reason = 7;
-  }
-  FS_MARK(6);
-  const i64 now = d.in->now_ms;
-  u32 npub_run = 0, nack_run = 0;   // the segment's publishes / acks so far (their ordinals)
-  for (u32 f0 = 0; f0 < kf; f0 += FS_NT) {
-    u32 f = f0 + tid;
-    u32 is_cmd = 0, nfr = 0;
-    u32 p = 0;
-    // every command's kind first: the publish / ack ordinals within the segment come out of
-    // the same block scan as the command index (no grid-wide rank scan over the commands)
-    Cmd c;
-    FInfo fi;
-    u32 cls = 0, mid = 0, hp = 0, gq = 0, gna = 0;
-    FInfo hi;
-    if (f < kf) {
-      p = CPOS(f);
-      if (b[p] == 1) {
-        is_cmd = 1;
-        if (be16(b + p + 7) == 60 && be16(b + p + 9) == 40) {
-          u32 e = f + 2;
-          while (e < kf && b[CPOS(e)] == 3) { ++nfr; ++e; }
-        }
-      }
-    }
-    if (is_cmd) {
-      fi = frame_at(b, p, L, fmax);
-      cls = be16(b + p + 7);
-      mid = be16(b + p + 9);
-      const i32 chs = fi.ch ? chan_lookup(d, conn, fi.ch) : -1;
-      c.pad[0] = (u32)chs;
-      if (cls == 60 && mid == 40 && chs >= 0) c.kind = CK_PUBLISH;
-      else if (cls == 60 && mid == 70 && chs >= 0 && dget_resolve(d, conn, b, p, fi.size, gq, gna)) c.kind = CK_GET;
-      else if (cls == 60 && mid == 80 && chs >= 0) c.kind = CK_ACK;
-      else if (cls == 60 && mid == 90 && chs >= 0) c.kind = CK_REJECT;
-      else if (cls == 60 && mid == 120 && chs >= 0) c.kind = CK_NACK;
-      else c.kind = CK_CONTROL;
-      if (c.kind != CK_CONTROL && c.kind != CK_GET && d.ch_tx[chs]) c.kind = CK_TXBUF;   // held until Tx.Commit
-      if (cls == 60 && mid == 40) {
-        hp = CPOS(f + 1);
-        hi = frame_at(b, hp, L, fmax);
-        // a publish too large for the carry is a control command: the host assembles it
-        if ((c.kind == CK_PUBLISH || c.kind == CK_TXBUF) && big_publish(d, fi.size, hi.size, be64(b + hp + 7 + 4), fmax))
-          c.kind = CK_CONTROL;
-      }
-    }
-    const u32 is_pub = is_cmd && c.kind == CK_PUBLISH;
-    const u32 is_ack = is_cmd && (c.kind == CK_ACK || c.kind == CK_NACK || c.kind == CK_REJECT);
-    // one scan of three 11-bit counters (<= FS_NT each per chunk): commands | pubs | acks
-    u32 tpk, tf;
-    const u32 rpk = block_scan<FS_NT>(is_cmd | (is_pub << 11) | (is_ack << 22), sc, tpk);
-    u32 fr = block_scan<FS_NT>(nfr, sc, tf);
-    const u32 r = rpk & 0x7ffu, tcnt = tpk & 0x7ffu;
-    if (one) {   // the segment's only chunk: reserve its commands / fragments now (as above)
-      if (tid == 0) {
-        const u32 cb = tcnt ? atomicAdd(&d.ctr->n_cmds, tcnt) : 0;
-        const u32 fb = tf ? atomicAdd(&d.ctr->n_frags, tf) : 0;
-        sh_frag_base = fb;
-        sh_cmd_base = cb;
-        sh_ncmd = (cb + tcnt > d.cmd_max || fb + tf > d.frag_max) ? 1u : 0u;
-      }
-      __syncthreads();
-      if (sh_ncmd && tcnt > 0) {   // (block-uniform) overflow: nothing is emitted, all carried
-        const u32 cb = sh_cmd_base;
-        for (u32 i = cb + tid; i < cb + tcnt && i < d.cmd_max; i += FS_NT) {
-          d.cmds[i].kind = CK_NONE;
-          d.cmd_is_pub[i] = 0;
-          d.cmd_is_ack[i] = 0;
-        }
-        __syncthreads();
-        if (tid == 0) sh_cmd_base = INVALID;
-        so.status |= SS_OVERFLOW;
-        so.status &= ~(SS_FRAME_ERROR | SS_UNEXPECTED);
-        consumed = 0;
-        kf = 0;
-        reason = 7;
-        break;
-      }
-      if (tcnt == 0 && tid == 0) sh_cmd_base = INVALID;
-    }
-    // the segment's Basic.Gets: a contiguous DGet range per chunk, in wire order
-    u32 gi = INVALID;
-    if (sh_get0 != INVALID) {   // (block-uniform)
-      const u32 is_get = is_cmd && c.kind == CK_GET;
-      u32 tg;
-      const u32 rg = block_scan<FS_NT>(is_get, sc, tg);
-      if (tid == 0) sh_gbase = tg ? atomicAdd(&d.tot[TS_NDGET], tg) : 0;
-      __syncthreads();
-      if (is_get) gi = sh_gbase + rg;
-    }
-    if (is_cmd) {
-      c.conn = conn;
-      c.ch = fi.ch;
-      c.m_off = OFF(p) + 7;
-      c.m_len = fi.size;
-      c.h_off = 0; c.h_len = 0; c.frag0 = 0; c.nfrag = 0; c.body_size = 0;
-      c.seg = s;
-      c.raw_off = OFF(p);
-      // ordinals within the segment: k_decode numbers publishes / acks segment-major
-      c.pad[1] = npub_run + ((rpk >> 11) & 0x7ffu);
-      c.pad[2] = nack_run + (rpk >> 22);
-      u32 endp = p + 8 + fi.size;
-      if (cls == 60 && mid == 40) {
-        c.h_off = OFF(hp) + 7;
-        c.h_len = hi.size;
-        c.body_size = (u32)be64(b + hp + 7 + 4);
-        c.frag0 = sh_frag_base + frun + fr;
-        c.nfrag = nfr;
-        endp = hp + 8 + hi.size;
-        for (u32 k = 0; k < nfr; ++k) {
-          u32 bp = CPOS(f + 2 + k);
-          FInfo bi = frame_at(b, bp, L, fmax);
-          Frag fg;
-          fg.off = OFF(bp) + 7;
-          fg.len = bi.size;
-          d.frags[c.frag0 + k] = fg;
-          endp = bp + 8 + bi.size;
-        }
-      }
-      c.raw_len = endp - p;
-      const u32 ci = sh_cmd_base + run + r;
-      if (gi != INVALID) {
-        if (gi < DGET_MAX) {
-          DGet g;
-          g.conn = conn; g.chslot = c.pad[0]; g.q = gq; g.noack = gna;
-          g.raw_off = c.raw_off; g.raw_len = c.raw_len; g.seg = s; g.pad = 0;
-          d.dget[gi] = g;
-        } else {
-          c.kind = CK_CONTROL;   // the step's DGet list is full: the host serves it (not paused)
-        }
-      }
-      d.cmds[ci] = c;
-      // classification for the rank scan of the large-segment-count path (k_decode)
-      d.cmd_is_pub[ci] = is_pub;
-      d.cmd_is_ack[ci] = is_ack;
-      if (c.kind == CK_CONTROL || c.kind == CK_TXBUF) {
-        u32 cbase;
-        u32 g = reserve_sat(&d.ctr->ctrl_bytes, c.raw_len, (u32)d.ctrl_cap, &cbase);
-        u32 ri = atomicAdd(&d.ctr->n_ctrl, 1u);
-        CtrlRec rec;
-        rec.conn = conn;
-        if (g == c.raw_len) {
-          for (u32 k = 0; k < c.raw_len; ++k) d.ctrl[cbase + k] = b[p + k];
-          rec.off = cbase; rec.len = c.raw_len;
-          rec.seg = c.kind == CK_TXBUF ? (CTRL_TXBUF | p) : gi != INVALID ? (CTRL_DGET | s) : s;
-        } else {   // control buffer full: an event, the host closes the connection (506)
-          rec.off = INVALID; rec.len = 506; rec.seg = 0;
-        }
-        if (ri < d.seg_max * 2) d.ctrl_rec[ri] = rec;
-      }
-    }
-    run += tcnt;
-    frun += tf;
-    npub_run += (tpk >> 11) & 0x7ffu;
-    nack_run += tpk >> 22;
-  }
-  if (tid == 0 && kf > 0) d.conn_last_rx[conn] = now;
-  if (reason == 0) so.status |= SS_CTRL;
-  if (tid == 0) {   // the segment's publish / ack counts: k_decode numbers them segment-major
-    d.seg_cmd_base[s] = (run && sh_cmd_base != INVALID) ? sh_cmd_base : INVALID;
-    d.seg_npub[s] = d.seg_cmd_base[s] == INVALID ? 0u : npub_run;
-    d.seg_nack[s] = d.seg_cmd_base[s] == INVALID ? 0u : nack_run;
-  }
-
-  FS_MARK(7);
-  // ---- (f) carry out: bytes [consumed, L)
-  u32 rest = L - consumed;
-  if (rest > d.carry_cap) { so.status |= SS_TOO_LARGE; rest = 0; }
-  else if (split) {   // [consumed, sp) from the work copy, the rest from the ingress slot (sp >= carry)
-    u8* const cd = d.carry + (u64)conn * d.carry_cap;
-    if (consumed < sp) block_copy(cd, d.work + wbase + consumed, sp - consumed, tid, FS_NT);
-    const u32 from = consumed > sp ? consumed : sp;
-    if (from < L) block_copy(cd + (from - consumed), seg_N + (from - seg_cl), L - from, tid, FS_NT);
-  } else block_copy(d.carry + (u64)conn * d.carry_cap, bg + consumed, rest, tid, FS_NT);   // 16-B moves from HBM
-  FS_MARK(8);
-  if (tid == 0) {
-    so.consumed = consumed;
-    so.carry = rest;
-    so.ncmds = run;
-    d.carry_len[conn] = rest;
-    if (reason == 0) d.conn_paused[conn] = 1;
-    d.seg_out[s] = so;
-  }
-#undef CPOS
-}
-
-// block-stride over the segments: the grid is capped below seg_max (a 1024-thread block
-// per segment slot of the capacity would mostly launch idle waves)
-__global__ __launch_bounds__(FS_NT) void k_frame_scan(DS d) {
-  const u32 nseg = d.in->nseg;
-  for (u32 s = blockIdx.x; s < nseg; s += gridDim.x) {
-    frame_scan_seg(d, s);
-    __syncthreads();   // the next segment reuses the LDS
-  }
-}
-
-// a Basic.Get the frame scan decoded that its step cannot serve (delivery window full, cold
-// queue head, step full, queue gone): its bytes go to the host as a control record flagged
-// CTRL_DGET -- the connection is not paused -- and the host serves it with a later step
-DEV void dget_to_host(const DS& d, u32 k) {
-  const DGet g = d.dget[k];
-  u32 cbase;
-  const u32 got = reserve_sat(&d.ctr->ctrl_bytes, g.raw_len, (u32)d.ctrl_cap, &cbase);
-  const u32 ri = atomicAdd(&d.ctr->n_ctrl, 1u);
-  CtrlRec rec;
-  rec.conn = g.conn;
-  if (got == g.raw_len) {
-    for (u32 k = 0; k < g.raw_len; ++k) d.ctrl[cbase + k] = d.work[g.raw_off + k];
-    rec.off = cbase; rec.len = g.raw_len; rec.seg = CTRL_DGET | g.seg;
-  } else {   // control buffer full: an event, the host closes the connection (506)
-    rec.off = INVALID; rec.len = 506; rec.seg = 0;
-  }
-  if (ri < d.seg_max * 2) d.ctrl_rec[ri] = rec;
-}
+#include "dp_frame_scan.h"
 
 // ============================================================================ K3 classify / decode
 DEV void set_counts(const DS& d, u32 np, u32 na) {
@@ -1629,7 +389,7 @@ __global__ __launch_bounds__(256) void k_decode(DS d) {
     __syncthreads();
     if (blockIdx.x * 256 >= n0) return;
   } else {
-    if (blockIdx.x == 0 && threadIdx.x == 0) set_counts(d, d.tot[4], d.tot[5]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) set_counts(d, d.tot[TS_CMD_PUBS], d.tot[TS_CMD_ACKS]);
     if (blockIdx.x * 256 >= n0) return;   // whole block idle
     if (seg_order) {
       u32 run = 0;
@@ -1790,7 +550,7 @@ __global__ __launch_bounds__(256) void k_decode(DS d) {
         pb.pad = (u32)(d.segs[c.seg].src + (fg.off - w0 - cl));
       }
     }
-    d.pubs[pi] = pb;   // (its channel's confirm count: k_marks)
+    d.pubs[pi] = pb;   // (its channel's confirm count: marks_range)
   } else if (c.kind == CK_ACK || c.kind == CK_NACK || c.kind == CK_REJECT) {
     const u32 ai = d.rank_scan ? d.cmd_ack_rank[i] : sprefa[c.seg] + c.pad[2];
     if (ai >= d.ack_max) return;
@@ -1804,7 +564,7 @@ __global__ __launch_bounds__(256) void k_decode(DS d) {
     if (c.kind == CK_ACK) { a.multiple = bits & 1; a.requeue = 0; }
     else if (c.kind == CK_REJECT) { a.multiple = 0; a.requeue = bits & 1; }
     else { a.multiple = bits & 1; a.requeue = (bits >> 1) & 1; }
-    d.acks[ai] = a;   // marked in the channel's window by k_marks (k_chan_advance resolves it)
+    d.acks[ai] = a;   // marked in the channel's window by marks_range (k_chan_advance resolves it)
   }
 }
 
@@ -1827,7 +587,6 @@ DEV void marks_range(const DS& d, u32 i0, u32 stride) {
     }
   }
 }
-__global__ __launch_bounds__(256) void k_marks(DS d) { marks_range(d, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256); }
 
 // ============================================================================ scans
 // single-block multi-array exclusive scan; n read from device; totals -> tot[slot+k]
@@ -2004,7 +763,7 @@ DEV void log_reserve(const DS& d);
 __global__ __launch_bounds__(1024) void k_scan_route(ScanArgs a, u32* tot, u64* status, u32* ctl, u32 smax, DS d) {
   const bool last = scan_tile<4, 4>(a, tot, status, ctl, smax);
   if (last) {
-    __syncthreads();   // the totals (tot[0..3]) were written by lane 0 of waves 0..3
+    __syncthreads();   // the totals (tot[TS_ROUTE..]) were written by lane 0 of waves 0..3
     if (threadIdx.x == 0) log_reserve(d);
   }
 }
@@ -2086,18 +845,18 @@ DEV void rs_offsets(const u32* hist, u32* hscan, u32 T, u32* lds) {
   }
 }
 
+// The occupied tiles' digit histograms of one pass (tile-stride over the blocks), then, in
+// the last block to finish (ticket), the tiles' offsets; true (block-uniform) in that block
 template <int DB>
-__global__ __launch_bounds__(RsNt<DB>::v) void k_rs_hist(const u32* keys, const u32* np, u32 shift, u32* hist,
-                                                        u32* hscan, u32* ticket, u32 ntiles) {
+DEV bool rs_hist_tiles(const u32* keys, u32 n, u32 shift, u32* hist, u32* hscan, u32* ticket, u32 ntiles) {
   constexpr u32 NT = RsNt<DB>::v, D = 1u << DB;
   __shared__ u32 cnt[D];
   __shared__ u32 lds[NT / 64 + 1];
   __shared__ u32 s_last;
   u32 tid = threadIdx.x, t = blockIdx.x;
-  u32 n = *np;
   u32 T = (n + SORT_TILE - 1) / SORT_TILE;
   if (T > ntiles) T = ntiles;
-  if (t >= T) return;   // only occupied tiles take part (and take a ticket)
+  if (t >= T) return false;   // only occupied tiles take part (and take a ticket)
   bool last = false;
   for (; t < T; t += gridDim.x) {   // tile-stride: the grid is capped below ntiles
     for (u32 k = tid; k < D; k += NT) cnt[k] = 0;
@@ -2118,10 +877,29 @@ __global__ __launch_bounds__(RsNt<DB>::v) void k_rs_hist(const u32* keys, const 
     __syncthreads();
     last = last || s_last;
   }
-  if (!last) return;
+  if (!last) return false;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   if (tid == 0) *ticket = 0;
   rs_offsets<DB>(hist, hscan, T, lds);
+  return true;
+}
+
+template <int DB>
+__global__ __launch_bounds__(RsNt<DB>::v) void k_rs_hist(const u32* keys, const u32* np, u32 shift, u32* hist,
+                                                        u32* hscan, u32* ticket, u32 ntiles) {
+  (void)rs_hist_tiles<DB>(keys, *np, shift, hist, hscan, ticket, ntiles);
+}
+
+// the lanes of this wave whose digit is dg (of the valid ones): one ballot per digit bit
+template <int DB>
+DEV u64 digit_peers(u32 dg, bool valid) {
+  u64 peers = __ballot(valid);
+#pragma unroll
+  for (u32 bb = 0; bb < DB; ++bb) {
+    const u64 m = __ballot((dg >> bb) & 1);
+    peers &= ((dg >> bb) & 1) ? m : ~m;
+  }
+  return peers;
 }
 
 template <int DB>
@@ -2143,12 +921,7 @@ __global__ __launch_bounds__(256) void k_rs_scatter(const u32* kin, const u32* v
       u32 i = wbase + c * 64 + lane;
       bool valid = i < n;
       u32 dg = valid ? (kin[i] >> shift) & (D - 1) : 0;
-      u64 peers = __ballot(valid);
-#pragma unroll
-      for (u32 bb = 0; bb < DB; ++bb) {
-        u64 m = __ballot((dg >> bb) & 1);
-        peers &= ((dg >> bb) & 1) ? m : ~m;
-      }
+      u64 peers = digit_peers<DB>(dg, valid);
       bool leader = valid && ((peers & lanemask_lt()) == 0);
       if (leader) wc[w][dg] += __popcll(peers);
       __builtin_amdgcn_wave_barrier();
@@ -2164,12 +937,7 @@ __global__ __launch_bounds__(256) void k_rs_scatter(const u32* kin, const u32* v
       bool valid = i < n;
       u32 key = valid ? kin[i] : 0;
       u32 dg = (key >> shift) & (D - 1);
-      u64 peers = __ballot(valid);
-#pragma unroll
-      for (u32 bb = 0; bb < DB; ++bb) {
-        u64 m = __ballot((dg >> bb) & 1);
-        peers &= ((dg >> bb) & 1) ? m : ~m;
-      }
+      u64 peers = digit_peers<DB>(dg, valid);
       u32 basepos = ((volatile u32*)wc[w])[dg];
       u32 rank = __popcll(peers & lanemask_lt());
       if (valid) {
@@ -2598,6 +1366,16 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
   }
 }
 
+// routing pass 0 of the group of 16 publishes [g0, g0 + 16) below n by a 1024-thread block:
+// the group's topic prefilter tiles, then wave w routes publish g0 + w
+DEV void route_group(const DS& d, u32 g0, u32 n, u32 w, u32 lane) {
+  topic_group(d, g0, n, w, lane);
+  __threadfence_block();
+  __syncthreads();
+  if (g0 + w < n) route_one<0>(d, g0 + w, lane);
+  __syncthreads();   // the next group's tiles overwrite nothing this group reads, but keep waves together
+}
+
 // routing pass 0 (count queues, destination ranks) of the step's own publishes, 16 per
 // 1024-thread block: the group's topic prefilter tiles on MFMA (fused k_topic_mfma), then
 // one wave per publish.  Pass 1 runs fused with the store (k_route_store) after
@@ -2617,20 +1395,14 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(ROUTE_WPE)
   // for capacity (2048 blocks), and the register allocator spills loop-invariant state to
   // scratch in the prologue -- 1 KB of HBM writes per idle wave otherwise (PMC WRITE_SIZE)
   if (lo + blockIdx.x * 16 >= n) return;
-  for (u32 g0 = lo + blockIdx.x * 16; g0 < n; g0 += gridDim.x * 16) {
-    topic_group(d, g0, n, w, lane);
-    __threadfence_block();
-    __syncthreads();
-    if (g0 + w < n) route_one<0>(d, g0 + w, lane);
-    __syncthreads();   // the next group's tiles overwrite nothing this group reads, but keep waves together
-  }
+  for (u32 g0 = lo + blockIdx.x * 16; g0 < n; g0 += gridDim.x * 16) route_group(d, g0, n, w, lane);
 }
 
 // reserve the step's contiguous body-log region and message-table indices
 DEV void log_reserve(const DS& d) {
-  u32 total = d.tot[1];     // slot bytes
-  u32 routed = d.tot[2];    // routed messages
-  u32 np = d.tot[TS_PAIR_BASE] + d.tot[0];
+  u32 total = d.tot[TS_ROUTE_SLOT_BYTES];
+  u32 routed = d.tot[TS_ROUTE_MSGS];
+  u32 np = d.tot[TS_PAIR_BASE] + d.tot[TS_ROUTE_PAIRS];
   d.tot[TS_PAIR_N] = np < d.pair_max ? np : d.pair_max;
   d.ctr->n_pairs = d.tot[TS_PAIR_N];
   // snowflake virtual position base for this step (ID_SLOT_BITS slots per wall-clock ms):
@@ -2650,8 +1422,8 @@ DEV void log_reserve(const DS& d) {
   }
   *d.log_step_base = head;
   *d.log_head = head + total;
-  d.tot[8] = *d.msg_free_top;
-  *d.msg_free_top = d.tot[8] - routed;
+  d.tot[TS_FREE_TOP] = *d.msg_free_top;
+  *d.msg_free_top = d.tot[TS_FREE_TOP] - routed;
   d.ctr->n_routed_msgs += routed;
   atomicAdd((unsigned long long*)d.live_bytes, (unsigned long long)total);
 }
@@ -2663,7 +1435,7 @@ DEV void log_reserve(const DS& d) {
 // starting at or after x (a prefix sum; binary search, all lanes in parallel).
 DEV void live_add_blocks(const DS& d, u32 lane) {
   const u64 head = *d.log_step_base;
-  const u32 total = d.tot[1];
+  const u32 total = d.tot[TS_ROUTE_SLOT_BYTES];
   if (head == INVALID || total == 0) return;
   const u32 lo = d.tot[TS_RANGE_LO];
   u32 hi = d.tot[TS_RANGE_HI];
@@ -2686,11 +1458,24 @@ DEV void live_add_blocks(const DS& d, u32 lane) {
   }
 }
 
+// a publish in slot layout at dst, by one wave: exchange, routing key, props, then (16-
+// aligned) its body fragments; w = the base its offsets are relative to
+DEV void write_slot(u8* dst, const u8* w, const Pub& pb, const Frag* frags) {
+  wave_copy(dst, w + pb.ex_off, pb.ex_len);
+  wave_copy(dst + pb.ex_len, w + pb.rk_off, pb.rk_len);
+  wave_copy(dst + pb.ex_len + pb.rk_len, w + pb.props_off, pb.props_len);
+  u32 bo = align16(pb.ex_len + pb.rk_len + pb.props_len);
+  for (u32 k = 0; k < pb.nfrag; ++k) {
+    Frag fg = frags[pb.frag0 + k];
+    wave_copy(dst + bo, w + fg.off, fg.len);
+    bo += fg.len;
+  }
+}
+
 // one wave per publish: write its queue pairs (route pass 1), then allocate the message,
 // fill its MsgEnt and copy exchange / rk / props / body into the log (fused k_route<1> +
 // k_store: one pass over the phase's publishes)
 DEV void store_one_pre(const DS& d, u32 p, u32 lane, const Pub& pb, u32 nq, u32 rr, u32 soff, u32 wbase);
-DEV void live_add_blocks(const DS& d, u32 lane);
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_route_store(DS d, u32 marks) {
   u32 lane = lane_id();
   if (blockIdx.x == 0 && threadIdx.x < 64) live_add_blocks(d, lane);
@@ -2724,7 +1509,7 @@ DEV void store_one_pre(const DS& d, u32 p, u32 lane, const Pub& pb, u32 nq, u32 
     }
     return;
   }
-  u32 msg = d.msg_free[d.tot[8] - 1 - rr];
+  u32 msg = d.msg_free[d.tot[TS_FREE_TOP] - 1 - rr];
   u64 off = base + soff;
   u8* slot = d.log + (off % d.log_bytes);
   const u8* w = pub_src(d, pb);
@@ -2735,15 +1520,7 @@ DEV void store_one_pre(const DS& d, u32 p, u32 lane, const Pub& pb, u32 nq, u32 
     uint4* dst = (uint4*)slot;
     for (u32 i = lane; i < (pb.slot_bytes >> 4); i += 64) dst[i] = src[i];
   } else {
-    wave_copy(slot, w + pb.ex_off, pb.ex_len);
-    wave_copy(slot + pb.ex_len, w + pb.rk_off, pb.rk_len);
-    wave_copy(slot + pb.ex_len + pb.rk_len, w + pb.props_off, pb.props_len);
-    u32 bo = meta;
-    for (u32 k = 0; k < pb.nfrag; ++k) {
-      Frag fg = d.frags[pb.frag0 + k];
-      wave_copy(slot + bo, w + fg.off, fg.len);
-      bo += fg.len;
-    }
+    write_slot(slot, w, pb, d.frags);
   }
   if (lane == 0) {
     MsgEnt m;
@@ -2787,6 +1564,21 @@ DEV void store_one_pre(const DS& d, u32 p, u32 lane, const Pub& pb, u32 nq, u32 
 // publish once per destination rank into [RDesc][payload] send buffers, laid out
 // destination-major so one RCCL all_to_all_single moves them.  Phase B imports the
 // received records as publishes and routes them against local queues only.
+
+// Inclusive scans, in place, of per-rank values over the wave's first WORLD_MAX lanes.
+// Variadic on purpose: a caller scans two or three values, and one call issues the shuffles
+// of all of them in each round before any of the adds, as the hand-written loops did; a
+// one-value helper called once per value made each value's chain of shuffles wait for the
+// one before (three times the dependent LDS round trips).
+template <class... U>
+DEV void world_scan(u32 lane, U&... x) {
+#pragma unroll
+  for (u32 o = 1; o < WORLD_MAX; o <<= 1) {
+    const u32 y[] = {__shfl_up(x, o, 64)...};
+    u32 k = 0;
+    if (lane >= o) ((x += y[k++]), ...);
+  }
+}
 
 // Per-destination record / byte offsets of the step's own publishes (phase A), without
 // any inter-block waiting: a block per 1024-publish tile ranks its records per wave and
@@ -2888,11 +1680,7 @@ __global__ __launch_bounds__(256) void k_pack(DS d) {
     const bool v = lane < d.world;
     const u32 c = v ? d.tot[TS_XSCAN + 2 * lane] : 0u, b = v ? d.tot[TS_XSCAN + 2 * lane + 1] : 0u;
     u32 sc = c, sb = b;
-#pragma unroll
-    for (u32 o = 1; o < WORLD_MAX; o <<= 1) {
-      const u32 yc = __shfl_up(sc, o, 64), yb = __shfl_up(sb, o, 64);
-      if (lane >= o) { sc += yc; sb += yb; }
-    }
+    world_scan(lane, sc, sb);   // (lane r = rank r)
     if (v) { s_base[lane] = sc - c; s_base[WORLD_MAX + lane] = sb - b; }
     if (blockIdx.x == 0) {
       if (v) { d.xs_base[lane] = sc - c; d.xs_base[WORLD_MAX + lane] = sb - b; d.xchg[lane] = c; d.xchg[WORLD_MAX + lane] = b; }
@@ -2922,16 +1710,7 @@ DEV void pack_one(const DS& d, u32 p, u32 lane, const u32* s_base) {
     const u32 meta = align16(pb.ex_len + pb.rk_len + pb.props_len);
     u32 sz = align16(meta + pb.body_size);
     if (di >= d.xfer_desc_max || po + sz > d.xfer_bytes) continue;  // overflow flagged by k_pack_bases
-    u8* o = d.send_pay + po;
-    wave_copy(o, w + pb.ex_off, pb.ex_len);
-    wave_copy(o + pb.ex_len, w + pb.rk_off, pb.rk_len);
-    wave_copy(o + pb.ex_len + pb.rk_len, w + pb.props_off, pb.props_len);
-    o += meta;
-    for (u32 k = 0; k < pb.nfrag; ++k) {
-      Frag fg = d.frags[pb.frag0 + k];
-      wave_copy(o, w + fg.off, fg.len);
-      o += fg.len;
-    }
+    write_slot(d.send_pay + po, w, pb, d.frags);
     if (lane == 0) {
       RDesc rd{};
       rd.pay_off = rel;
@@ -2976,11 +1755,7 @@ __global__ __launch_bounds__(1024) void k_import_route(DS d) {
     const u32 an = v ? d.xchg[XC_RECV_AN + lane] : 0u, ab = v ? d.xchg[XC_RECV_AB + lane] : 0u;
     const u32 rk = (v && d.links) ? d.xchg[XC_RACK_N + lane] : 0u;
     u32 sn = cn, sb = cb, sk = rk;
-#pragma unroll
-    for (u32 o = 1; o < WORLD_MAX; o <<= 1) {
-      const u32 yn = __shfl_up(sn, o, 64), yb = __shfl_up(sb, o, 64), yk = __shfl_up(sk, o, 64);
-      if (lane >= o) { sn += yn; sb += yb; sk += yk; }
-    }
+    world_scan(lane, sn, sb, sk);   // (lane r = source r)
     if (v) { xr[lane] = sn - cn; xr[WORLD_MAX + lane] = sb - cb; xr[2 * WORLD_MAX + lane] = an; xr[3 * WORLD_MAX + lane] = ab; }
     const u32 last = d.world - 1;
     const u32 dsum = (u32)__shfl((int)sn, (int)last), psum = (u32)__shfl((int)sb, (int)last);
@@ -3013,11 +1788,7 @@ __global__ __launch_bounds__(1024) void k_import_route(DS d) {
     if (tid < 16 && g0 + tid < n) import_one(d, g0 + tid, xr);
     __threadfence_block();
     __syncthreads();
-    topic_group(d, base + g0, base + n, w, lane);
-    __threadfence_block();
-    __syncthreads();
-    if (g0 + w < n) route_one<0>(d, base + g0 + w, lane);
-    __syncthreads();
+    route_group(d, base + g0, base + n, w, lane);
   }
 }
 
@@ -3146,18 +1917,24 @@ DEV u32 enq_store(const DS& d, const EnqLoad& l, u32 q, u32 rank, bool last, Per
   }
   return drop;
 }
-DEV u32 enqueue_at(const DS& d, u32 q, u32 p, u32 rank, bool last, PersistRec* pr) {
-  return enq_store(d, enq_load(d, q, p), q, rank, last, pr);
-}
-DEV u32 enqueue_one(const DS& d, u32 src, u32 i, u32 n, PersistRec* pr, u32 hs_ntiles) {
+DEV u32 enqueue_one(const DS& d, u32 src, u32 i, u32 n, PersistRec* pr) {
   const u32* kk = d.pair_k[src];
   const u32 rb = d.rank_bits;
   u32 q = kk[i] >> rb;
   u32 p = d.pair_v[src][i];
-  // single-pass sort (queue|rank key <= 8 bits): the queue's first pair is where digit
-  // (q << rank_bits) starts; otherwise k_qfirst recorded it
-  u32 first = hs_ntiles ? d.hist_scan[q << rb] : d.q_first[q];
-  return enqueue_at(d, q, p, i - first, (i + 1 == n) || (kk[i + 1] >> rb) != q, pr);
+  u32 first = d.q_first[q];   // the queue's first pair (k_qfirst)
+  return enq_store(d, enq_load(d, q, p), q, i - first, (i + 1 == n) || (kk[i + 1] >> rb) != q, pr);
+}
+// after a pair's enqueue (whole waves: wave collectives): release the message a full ring
+// dropped and count it; record a persistent message's enqueue for the store
+DEV void enqueue_done(const DS& d, u32 drop, const PersistRec& pr) {
+  wave_release(d, drop, drop != INVALID);
+  if (drop != INVALID) atomicAdd(&d.ctr->n_ring_full, 1u);
+  if (d.persist) {
+    const bool want = pr.msg != INVALID;
+    const u32 k = wave_reserve(&d.ctr->n_persist, want);
+    if (want && k < d.persist_max) d.prec[k] = pr;
+  }
 }
 
 // ---- unbounded queues (QueueEntity.scala:271-316 keeps a growing Vector): before the
@@ -3167,13 +1944,21 @@ DEV u32 enqueue_one(const DS& d, u32 src, u32 i, u32 n, PersistRec* pr, u32 hs_n
 // max_capacity.  Positions stay absolute (entry pos lives at off + (pos & mask)), so
 // unacked windows, requeues and store rows keep their queue offsets.
 DEV void plan_queue(const DS& d, u32 q, u64 cnt);
-DEV void ring_plan_one(const DS& d, u32 src, u32 hs_ntiles, u32 i, u32 n) {
+// copy every moved (grown) ring's live entries to its new place, by the nt threads of a block
+DEV void copy_moved_rings(const DS& d, u32 nm, u32 tid, u32 nt) {
+  for (u32 m = 0; m < nm; ++m) {
+    const RingMove mv = d.moves[m];
+    for (u64 pos = mv.head + tid; pos < mv.tail; pos += nt)
+      d.ring[mv.new_off + (pos & mv.new_mask)] = d.ring[mv.old_off + (pos & mv.old_mask)];
+  }
+}
+
+DEV void ring_plan_one(const DS& d, u32 src, u32 i, u32 n) {
   const u32* kk = d.pair_k[src];
   const u32 rb = d.rank_bits;
   const u32 q = kk[i] >> rb;
   if (i + 1 < n && (kk[i + 1] >> rb) == q) return;   // not the queue's last pair
-  const u32 first = hs_ntiles ? d.hist_scan[q << rb] : d.q_first[q];
-  plan_queue(d, q, (u64)(i - first) + 1);
+  plan_queue(d, q, (u64)(i - d.q_first[q]) + 1);
 }
 // queue q takes cnt entries this step: record its tail before the enqueue, grow its ring
 DEV void plan_queue(const DS& d, u32 q, u64 cnt) {
@@ -3212,13 +1997,13 @@ DEV void plan_queue(const DS& d, u32 q, u64 cnt) {
 // k_ring_moves: growth is rare, so one block does it and the common step saves a launch)
 // Grid-stride over the pairs with a capped grid (the graph's grid is sized for pair_max;
 // a block per 256 pairs of the capacity would mostly launch waves with nothing to do)
-__global__ __launch_bounds__(256) void k_ring_plan(DS d, u32 src, u32 hs_ntiles) {
+__global__ __launch_bounds__(256) void k_ring_plan(DS d, u32 src) {
   __shared__ u32 s_last;
   const u32 n = d.tot[TS_PAIR_N];
   u32 nb = (n + 255) / 256;
   if (nb > gridDim.x) nb = gridDim.x;   // blocks taking part
   if (blockIdx.x >= nb) return;
-  for (u32 i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) ring_plan_one(d, src, hs_ntiles, i, n);
+  for (u32 i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) ring_plan_one(d, src, i, n);
   // a thread that planned a ring move fenced it itself (rare); the common step only waits
   // for its own stores before the ticket (no L2 writeback per block)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -3228,15 +2013,10 @@ __global__ __launch_bounds__(256) void k_ring_plan(DS d, u32 src, u32 hs_ntiles)
   if (!s_last) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   if (threadIdx.x == 0) d.tot[TS_RP_TICKET] = 0;
-  const u32 nm = d.tot[TS_NMOVE];
-  for (u32 m = 0; m < nm; ++m) {
-    const RingMove mv = d.moves[m];
-    for (u64 pos = mv.head + threadIdx.x; pos < mv.tail; pos += 256)
-      d.ring[mv.new_off + (pos & mv.new_mask)] = d.ring[mv.old_off + (pos & mv.old_mask)];
-  }
+  copy_moved_rings(d, d.tot[TS_NMOVE], threadIdx.x, 256);
 }
 
-__global__ void k_enqueue(DS d, u32 src, u32 hs_ntiles) {
+__global__ void k_enqueue(DS d, u32 src) {
   const u32 n = d.tot[TS_PAIR_N];
   const u32 stride = gridDim.x * blockDim.x;
   // whole waves iterate together (the wave collectives below need every lane)
@@ -3244,14 +2024,8 @@ __global__ void k_enqueue(DS d, u32 src, u32 hs_ntiles) {
     const u32 i = b + threadIdx.x;
     PersistRec pr;
     pr.msg = INVALID;
-    u32 drop = i < n ? enqueue_one(d, src, i, n, &pr, hs_ntiles) : INVALID;
-    wave_release(d, drop, drop != INVALID);
-    if (drop != INVALID) atomicAdd(&d.ctr->n_ring_full, 1u);
-    if (d.persist) {
-      bool want = pr.msg != INVALID;
-      u32 k = wave_reserve(&d.ctr->n_persist, want);
-      if (want && k < d.persist_max) d.prec[k] = pr;
-    }
+    u32 drop = i < n ? enqueue_one(d, src, i, n, &pr) : INVALID;
+    enqueue_done(d, drop, pr);
   }
 }
 
@@ -3274,53 +2048,18 @@ DEV void plan_rings_block(const DS& d, const u32* hscan, u32 n, u32 D, u32 tid, 
   const u32 nm = __hip_atomic_load(&d.tot[TS_NMOVE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!nm) return;   // (block-uniform) rings that grew: copy their live entries over
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  for (u32 m = 0; m < nm; ++m) {
-    const RingMove mv = d.moves[m];
-    for (u64 pos = mv.head + tid; pos < mv.tail; pos += nt)
-      d.ring[mv.new_off + (pos & mv.new_mask)] = d.ring[mv.old_off + (pos & mv.old_mask)];
-  }
+  copy_moved_rings(d, nm, tid, nt);
 }
 
 template <int DB>
 __global__ __launch_bounds__(RsNt<DB>::v) void k_rs_hist_plan(DS d, const u32* keys, const u32* np, u32* hist,
                                                              u32* hscan, u32* ticket, u32 ntiles) {
-  constexpr u32 NT = RsNt<DB>::v, D = 1u << DB;
-  __shared__ u32 cnt[D];
-  __shared__ u32 lds[NT / 64 + 1];
-  __shared__ u32 s_last;
-  u32 tid = threadIdx.x, t = blockIdx.x;
   const u32 n = *np;
-  u32 T = (n + SORT_TILE - 1) / SORT_TILE;
-  if (T > ntiles) T = ntiles;
-  if (T == 0) {   // no pairs: nothing to plan (the queues' tails stay)
-    return;
-  }
-  if (t >= T) return;
-  bool last = false;
-  for (; t < T; t += gridDim.x) {
-    for (u32 k = tid; k < D; k += NT) cnt[k] = 0;
-    __syncthreads();
-    const u32 base = t * SORT_TILE;
-    for (u32 j = 0; j < SORT_TILE / NT; ++j) {
-      const u32 i = base + j * NT + tid;
-      if (i < n) atomicAdd(&cnt[keys[i] & (D - 1)], 1u);
-    }
-    __syncthreads();
-    for (u32 k = tid; k < D; k += NT)
-      __hip_atomic_store(&hist[t * D + k], cnt[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (tid == 0) s_last = atomicAdd(ticket, 1u) == T - 1;
-    __syncthreads();
-    last = last || s_last;
-  }
-  if (!last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  if (tid == 0) *ticket = 0;
-  rs_offsets<DB>(hist, hscan, T, lds);
+  if (n == 0) return;   // no pairs (T == 0): nothing to plan (the queues' tails stay)
+  if (!rs_hist_tiles<DB>(keys, n, 0u, hist, hscan, ticket, ntiles)) return;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __syncthreads();
-  plan_rings_block(d, hscan, n, D, tid, NT);
+  plan_rings_block(d, hscan, n, 1u << DB, threadIdx.x, RsNt<DB>::v);
 }
 
 template <int DB>
@@ -3352,13 +2091,7 @@ __global__ __launch_bounds__(256) void k_rs_scatter_enq(DS d, const u32* kin, co
     for (u32 c = 0; c < CH; ++c) {   // per-wave digit counts
       const bool valid = wbase + c * 64 + lane < n;
       const u32 dg = key[c] & (D - 1);
-      u64 peers = __ballot(valid);
-#pragma unroll
-      for (u32 bb = 0; bb < DB; ++bb) {
-        const u64 m = __ballot((dg >> bb) & 1);
-        peers &= ((dg >> bb) & 1) ? m : ~m;
-      }
-      pe[c] = peers;
+      const u64 peers = pe[c] = digit_peers<DB>(dg, valid);
       if (valid && ((peers & lt) == 0)) wc[w][dg] += __popcll(peers);
       __builtin_amdgcn_wave_barrier();
     }
@@ -3399,13 +2132,7 @@ __global__ __launch_bounds__(256) void k_rs_scatter_enq(DS d, const u32* kin, co
       pr.msg = INVALID;
       u32 drop = INVALID;
       if (valid) drop = enq_store(d, el[c], key[c] >> rb, pos[c] - first[c], pos[c] + 1 == nx[c], &pr);
-      wave_release(d, drop, drop != INVALID);
-      if (drop != INVALID) atomicAdd(&d.ctr->n_ring_full, 1u);
-      if (d.persist) {
-        const bool want = pr.msg != INVALID;
-        const u32 k = wave_reserve(&d.ctr->n_persist, want);
-        if (want && k < d.persist_max) d.prec[k] = pr;
-      }
+      enqueue_done(d, drop, pr);
     }
   }
 }
@@ -3678,7 +2405,7 @@ DEV void unreserve(const DS& d, u32 c, u32 take) {
 
 // one block per queue: TTL skip (K12, wave 0), credit-limited round-robin split over the
 // consumers (thread 0, deterministic consumer order), egress byte budget (block-parallel
-// sizes), then one delivery run per granted consumer.  k_runs orders the runs by channel
+// sizes), then one delivery run per granted consumer.  runs_body orders the runs by channel
 // and k_dv_write expands them into Deliv records at their final positions, so no sort
 // over individual deliveries is needed (QueueEntity.scala:318-393, FrameStage.scala:380-406).
 #define REQ_BLK 1024
@@ -3740,7 +2467,7 @@ DEV void spill_queue(const DS& d, u32 q, u64 lim, u32 hot, u32 budget, u64* move
   if (threadIdx.x == 0) d.q_spill_cur[q] = s_open == ~0ull ? tail : (u64)s_open;
 }
 
-// true: the block wrote runs with plain stores (the fused k_runs' ticket needs an
+// true: the block wrote runs with plain stores (the ticket before runs_body needs an
 // agent-scope release); false: at most q_nruns[q] = 0, stored agent-coherent
 // a consumer's dispatch inputs, loaded by the block's other waves while wave 0 walks the
 // TTL head (thread 0's credit loop then reads them from LDS: only its atomics stay serial)
@@ -4045,7 +2772,7 @@ DEV bool dequeue_queue(const DS& d) {
         qp += keep;
       }
     }
-    // (3) delivery slots (capacity), trimmed from the last run backwards; k_runs
+    // (3) delivery slots (capacity), trimmed from the last run backwards; runs_body
     // rewrites n_deliv with the exact total of the kept runs
     u32 total = 0;
     for (u32 j = 0; j < m; ++j) total += g_n[j];
@@ -4086,9 +2813,9 @@ DEV bool dequeue_queue(const DS& d) {
 }
 
 // K8 dequeue, one block per queue; the last block to finish (ticket) then lays out the
-// step's delivery runs (fused k_runs: a launch less per step)
+// step's delivery runs (runs_body, once the kernel k_runs: a launch less per step)
 template <u32 NT> DEV void runs_body(const DS& d, u64* key_lds, u32 key_cap, u32* lds);
-#define DQ_RUN_LDS 2048   // runs sorted in the fused k_runs' LDS (more: the global-memory sort)
+#define DQ_RUN_LDS 2048   // runs that runs_body sorts in LDS (more: the global-memory sort)
 __global__ __launch_bounds__(256) void k_dequeue(DS d) {
   __shared__ u64 key_lds[DQ_RUN_LDS];
   __shared__ u32 lds[256 / 64 + 1];
@@ -4184,13 +2911,7 @@ DEV void runs_body(const DS& d, u64* key_lds, u32 key_cap, u32* lds) {
     d.ctr->n_deliv = run;   // the saturating slot counter may have ended above deliv_max
   }
 }
-__global__ __launch_bounds__(1024) void k_runs(DS d) {
-  __shared__ u64 key_lds[RUN_SORT_LDS];
-  __shared__ u32 lds[1024 / 64 + 1];
-  runs_body<1024>(d, key_lds, RUN_SORT_LDS, lds);
-}
 
-DEV void wave_consumed(const DS& d, u32 msg, u32 q, u64 qpos, u32 kind, bool valid);
 // thread per delivery: expand its run (binary search), assign the channel's next delivery
 // tag, fill the unacked window slot, size the rendered frames
 #define DVW_LDS 512   // runs staged in LDS per block (more: searched in global memory)
@@ -4369,7 +3090,7 @@ __global__ __launch_bounds__(1024) void k_conn_layout(DS d) {
       acc += all;
       __syncthreads();   // lds of the next pass's scan
     }
-    if (threadIdx.x == 0) d.tot[6] = acc;
+    if (threadIdx.x == 0) d.tot[TS_DELIV_BYTES] = acc;
     __syncthreads();
   }
   u32 run = 0;
@@ -4889,7 +3610,6 @@ DEV void copy16(u8* dst, const u8* src, u64 n, u64 gtid, u64 gsz) {
   for (u64 i = (nv << 4) + gtid; i < n; i += gsz) dst[i] = src[i];
 }
 
-DEV void host_out_copies(const DS& d, u64 gtid, u64 gsz);
 __global__ __launch_bounds__(256) void k_host_out(DS d) {
   if (blockIdx.x == 0 && threadIdx.x == 0) final_step(d);   // log tail, counters -> host
   host_out_copies(d, blockIdx.x * blockDim.x + threadIdx.x, (u64)gridDim.x * blockDim.x);

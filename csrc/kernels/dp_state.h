@@ -1,5 +1,5 @@
 // Device-state descriptor passed by value to every data-plane kernel.
-// All arrays are allocated once by Engine (engine.cpp) and sized from EngineCfg;
+// All arrays are allocated once by Engine (engine.hip) and sized from EngineCfg;
 // nothing is allocated on the step path, so the whole step is hipGraph-capturable.
 #pragma once
 #include "dp_common.h"
@@ -16,7 +16,6 @@
 #define INGRESS_SLOTS 3       // rotating ingress payload buffers (StepIn.ingress)
 #define EGRESS_SLOTS 4        // rotating egress buffers (render of step t || D2H of t-1 .. t-3)
 #define RUNS_PER_Q 64         // consumers served per queue per step (dequeue round-robin window)
-#define RUN_SORT_LDS 8192     // runs sorted in LDS by k_runs (more: global-memory sort)
 #define SPILL_LAG 6           // steps a freed spill-ring byte stays untouched (egress by reference)
 
 // host-mapped xchg[] words (one array per IO parity).  [XC_SEND_N + r] / [XC_SEND_B + r]:
@@ -36,11 +35,19 @@ enum : u32 {
 
 // tot[] scratch slots (scan totals and phase bookkeeping)
 enum : u32 {
+  TS_ROUTE = 0,                         // the route scan's four totals (k_scan_route), of the phase:
+  TS_ROUTE_PAIRS = 0, TS_ROUTE_SLOT_BYTES = 1, TS_ROUTE_MSGS = 2,   // pairs, body-log bytes, routed
+  TS_ROUTE_RET_BYTES = 3,               // messages, Basic.Return bytes
+  TS_CMD_PUBS = 4, TS_CMD_ACKS = 5,     // the command scan's totals: publishes, acks
+  TS_DELIV_BYTES = 6,                   // the delivery-size scan's total
+  TS_CONN_BYTES = 7,                    // the connection-layout scan's total
+  TS_FREE_TOP = 8,                      // msg_free_top before the phase's reservation (log_reserve)
+  TS_WORK_USED = 15,                    // work-buffer bytes the step's segments take (k_stage)
   TS_RANGE_LO = 20, TS_RANGE_HI = 21,   // publish index range of the current routing phase
   TS_PAIR_BASE = 22, TS_PAIR_N = 23,    // pair base of the phase / pairs so far
   TS_NIMPORT = 24, TS_IMPORT_BASE = 25, // imported records / their work-buffer base
   TS_PERSIST = 26,                      // packed persist bytes
-  TS_NRUNS = 27,                        // delivery runs of the step (k_runs)
+  TS_NRUNS = 27,                        // delivery runs of the step (k_dequeue's last block)
   TS_REQ_TICKET = 28,                   // k_requeue finished-block ticket (last block compacts)
   TS_RS_TICKET = 29,                    // k_rs_hist finished-block ticket (last block: offsets)
   TS_NMOVE = 30,                        // rings moved (grown) this step (k_ring_plan)
@@ -268,8 +275,9 @@ struct DS {
   u32* dv_size;             // by sorted position
   u32* dv_off;
   u32* ch_first;            // [chslots] scratch
-  // delivery runs: k_dequeue emits one run per (queue, consumer) grant, k_runs orders
-  // them by channel, k_dv_write expands them into Deliv records at their final positions
+  // delivery runs: k_dequeue emits one run per (queue, consumer) grant, its last block
+  // (runs_body) orders them by channel, k_dv_write expands them into Deliv records at their
+  // final positions
   Run* runs;                // [q_max * RUNS_PER_Q]
   u32* q_nruns;             // [q_max] runs of the queue this step
   u32* run_order;           // [q_max * RUNS_PER_Q] run slots in delivery order
@@ -282,7 +290,6 @@ struct DS {
   u32* req_q_n;             // per queue count
 
   // ---------------- scratch
-  u32* scan_tmp;            // block sums
   u32* hist;                // radix histograms
   u32* hist_scan;
   u32* tot;                 // scan totals [64]
@@ -300,10 +307,8 @@ struct DS {
   u32* conn_gempty;         // per connection: Basic.GetEmpty frames to render this step
   u32* conn_gempty_ch;      // per connection: their channel number
   u32* pub_rmask;           // [pub_cap] remote ranks owning >= 1 routed queue
-  u32* xp_cnt;              // [world][pub_cap] record for rank r?
-  u32* xp_cnt_off;
-  u32* xp_byt;              // [world][pub_cap] payload bytes for rank r
-  u32* xp_byt_off;
+  u32* xp_cnt_off;          // [world][pub_cap] record index within its 1024-publish tile, for rank r
+  u32* xp_byt_off;          // [world][pub_cap] payload byte offset within the tile, for rank r
   u32* xs_base;             // [2*WORLD_MAX] send record / byte bases per destination
   u32* pk_agg;              // [pub tiles][2*WORLD_MAX] k_pack_scan tile aggregates -> prefixes
   u32* xr_base;             // [2*WORLD_MAX] recv record / byte bases per source
@@ -327,8 +332,6 @@ struct DS {
   // them to the store without copying them on its stepper thread
   u8* ps_persist[PSLOTS];      // [persist_bytes]
   ConsumedRec* ps_crec[PSLOTS];  // [persist_max]
-  u8* persist_h;            // host-mapped [persist_bytes]
-  ConsumedRec* crec_h;      // host-mapped [persist_max]
 
   // ---------------- remote-consumer links (X2/X3; links == 0: unused).  Owner side: a
   // link pseudo-connection's deliveries are not rendered as frames but shipped as restore

@@ -380,9 +380,7 @@ class Engine {
     d_.conn_gempty = (u32*)dev("conn_gempty", 4ull * d_.c_max);
     d_.conn_gempty_ch = (u32*)dev("conn_gempty_ch", 4ull * d_.c_max);
     d_.pub_rmask = (u32*)dev("pub_rmask", 4ull * d_.pub_cap);
-    d_.xp_cnt = nullptr;   // (per-rank count arrays: k_pack_scan counts in registers)
     d_.xp_cnt_off = (u32*)dev("xp_cnt_off", 4 * xw);
-    d_.xp_byt = nullptr;
     d_.xp_byt_off = (u32*)dev("xp_byt_off", 4 * xw);
     // k_pack_scan: per-tile aggregates / prefixes (2 * WORLD_MAX values per 1024 publishes)
     d_.pk_agg = (u32*)dev("pk_agg", 4ull * 2 * WORLD_MAX * (ceil_div(d_.pub_max ? d_.pub_max : 1, 1024) + 1));
@@ -551,7 +549,6 @@ class Engine {
     ntiles_max_ = ceil_div(d_.pair_max, SORT_TILE);
     d_.hist = (u32*)dev("hist", 4ull * 2048 * ntiles_max_);        // up to 11-bit digits
     d_.hist_scan = (u32*)dev("hist_scan", 4ull * 2048 * ntiles_max_);
-    d_.scan_tmp = (u32*)dev("scan_tmp", 4ull * 1024);
     {   // look-back scan state: status words for the largest scan, ticket/epoch
       u64 big = d_.pub_cap > d_.cmd_max ? d_.pub_cap : d_.cmd_max;
       big = big > d_.deliv_max ? big : d_.deliv_max;
@@ -2709,7 +2706,7 @@ class Engine {
     hipLaunchKernelGGL(k_frame_scan, capped(d.seg_max, n_cu_), dim3(FS_NT), 0, s, d);
     if (d.rank_scan)
       launch_scan(s, d, {{d.cmd_is_pub, d.cmd_pub_rank}, {d.cmd_is_ack, d.cmd_ack_rank}}, &d.ctr->n_cmds,
-                  d.cmd_max, 4, nullptr, /*ingest=*/true);
+                  d.cmd_max, TS_CMD_PUBS, nullptr, /*ingest=*/true);
     hipLaunchKernelGGL(k_decode, blocks(d.cmd_max, 256), dim3(256), 0, s, d);
   }
 
@@ -2726,7 +2723,7 @@ class Engine {
     // scan of the routing counts + the phase's log reservation, then pairs + store
     const ScanArgs a = scan_args({{d.pub_nq, d.pub_pair_off}, {d.pub_slot, d.pub_slot_off},
                                   {d.pub_routed, d.pub_routed_rank}, {d.pub_ret_sz, d.pub_ret_off}},
-                                 &d.tot[TS_RANGE_HI], d.pub_cap, 0, &d.tot[TS_RANGE_LO]);
+                                 &d.tot[TS_RANGE_HI], d.pub_cap, TS_ROUTE, &d.tot[TS_RANGE_LO]);
     hipLaunchKernelGGL(k_scan_route, dim3(ceil_div(d.pub_cap ? d.pub_cap : 1, SCAN_TILE)), dim3(1024), 0, s, a, d.tot,
                        scan_status_, scan_ctl_, scan_smax_, d);
     hipLaunchKernelGGL(k_route_store, wave_blocks(nmax), dim3(256), 0, s, d, imports ? 0u : 1u);
@@ -2764,8 +2761,8 @@ class Engine {
       u32* pv[2] = {d.pair_v[0], d.pair_v[1]};
       const u32 psrc = radix_sort(s, d, pk, pv, &d.tot[TS_PAIR_N], d.pair_max, pbits);
       hipLaunchKernelGGL(k_qfirst, blocks(d.pair_max, 256), dim3(256), 0, s, d, psrc);
-      hipLaunchKernelGGL(k_ring_plan, capped(ceil_div(d.pair_max, 256), 1024), dim3(256), 0, s, d, psrc, 0u);
-      hipLaunchKernelGGL(k_enqueue, capped(ceil_div(d.pair_max, 256), 1024), dim3(256), 0, s, d, psrc, 0u);
+      hipLaunchKernelGGL(k_ring_plan, capped(ceil_div(d.pair_max, 256), 1024), dim3(256), 0, s, d, psrc);
+      hipLaunchKernelGGL(k_enqueue, capped(ceil_div(d.pair_max, 256), 1024), dim3(256), 0, s, d, psrc);
     }
     // without persistence nothing runs after k_post: it also writes the host-visible
     // outputs and its last block the counters (fused k_host_out)
@@ -2779,14 +2776,14 @@ class Engine {
     hipLaunchKernelGGL(k_chan_advance, capped(nch, 1024), dim3(256), 0, s, d);
     // k_dequeue first puts requeued deliveries back in front of their queues' heads, in
     // queue-offset order (QueueEntity.scala:415-446), then dispatches
-    hipLaunchKernelGGL(k_dequeue, dim3(d.q_max), dim3(256), 0, s, d);   // (its last block: k_runs)
+    hipLaunchKernelGGL(k_dequeue, dim3(d.q_max), dim3(256), 0, s, d);   // (its last block lays out the runs)
     hipLaunchKernelGGL(k_dv_write, blocks(d.deliv_max, 256), dim3(256), 0, s, d);
     if (d.c_max <= CONN_LAYOUT_MAX) {
       hipLaunchKernelGGL(k_conn_layout, dim3(1), dim3(1024), 0, s, d);   // + the delivery-size scan
     } else {
-      launch_scan(s, d, {{d.dv_size, d.dv_off}}, &d.ctr->n_deliv, d.deliv_max, 6);
+      launch_scan(s, d, {{d.dv_size, d.dv_off}}, &d.ctr->n_deliv, d.deliv_max, TS_DELIV_BYTES);
       hipLaunchKernelGGL(k_conn_sizes, blocks(d.c_max, 256), dim3(256), 0, s, d);
-      launch_scan(s, d, {{d.conn_total, d.conn_base}}, nullptr, d.c_max, 7);
+      launch_scan(s, d, {{d.conn_total, d.conn_base}}, nullptr, d.c_max, TS_CONN_BYTES);
       hipLaunchKernelGGL(k_conn_out, blocks(d.c_max, 256), dim3(256), 0, s, d);
     }
     if (d.links) hipLaunchKernelGGL(k_link_bases, dim3(1), dim3(64), 0, s, d);
