@@ -1054,6 +1054,12 @@ class GpuDataPlane(ControlState):
         same payload.  Returns False when not applicable (nothing queued)."""
         return bool(self.eng.prefetch(int(payload_ptr), int(payload_len)))
 
+    def h2d_stats(self):
+        """Payload copies so far by path -- ``split`` (two halves on two SDMA engines),
+        ``unsplit`` (whole, on the ingress engine), ``runtime`` (a runtime copy: pageable
+        memory or h2d_hsa off) -- and the ``engine`` / ``engine2`` the HSA path uses (-1: none)."""
+        return dict(self.eng.h2d_stats())
+
     def submit_lockstep(self, segs, payload_ptr, payload_len, now_ms=None):
         """One lockstep step of a sharded plane on the engine's native exchange (RCCL over
         xGMI, or host shared memory), in the order the native front end's sharded stepper

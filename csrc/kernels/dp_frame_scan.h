@@ -169,7 +169,20 @@ DEV bool dget_resolve(const DS& d, u32 conn, const u8* b, u32 p, u32 size, u32& 
   return false;
 }
 
-DEV void frame_scan_seg(const DS& d, const u32 s) {
+// a segment's descriptor and the connection state its scan starts from: nothing of the
+// ingress slot, so a block loads its first segment's before it waits for the payload copy
+struct FsHead { u32 conn, L, seg_len, src, fmax; };
+DEV FsHead fs_head(const DS& d, const u32 s) {
+  FsHead h;
+  h.conn = d.segs[s].conn;
+  h.L = d.seg_total[s];
+  h.seg_len = d.segs[s].len;
+  h.src = d.segs[s].src;
+  h.fmax = d.conn_frame_max[h.conn];
+  return h;
+}
+
+DEV void frame_scan_seg(const DS& d, const u32 s, const FsHead hd) {
   __shared__ uint4 fs_pool[FS_POOL / 16];
   __shared__ u32 sc[FS_NT / 64 + 1];
   __shared__ u32 sh_m, sh_over, sh_ok, sh_nf, sh_stop, sh_brk;
@@ -178,9 +191,9 @@ DEV void frame_scan_seg(const DS& d, const u32 s) {
   __shared__ u32 sh_split;   // split mode: bytes [0, sh_split) are in the work buffer
 
   const u32 tid = threadIdx.x;
-  const u32 conn = d.segs[s].conn;
-  const u32 L = d.seg_total[s];
-  const u32 seg_len = d.segs[s].len, seg_cl = L - seg_len, src = d.segs[s].src;
+  const u32 conn = hd.conn;
+  const u32 L = hd.L;
+  const u32 seg_len = hd.seg_len, seg_cl = L - seg_len, src = hd.src;
   // the step's new bytes are read where their H2D put them: the ingress slots follow the
   // work buffers in one allocation, so a u32 offset from d.work reaches them, and every
   // later reader (decode, route-store, returns, gets) takes a frame's bytes from there.  A
@@ -213,10 +226,10 @@ DEV void frame_scan_seg(const DS& d, const u32 s) {
   u16* const amask = chain_am;
   int16_t* const csucc = (int16_t*)(chain_am + (staged ? FS_CAND_STAGED : (CAND_MAX > FS_AM_MAX ? CAND_MAX : FS_AM_MAX)));
   u8* const claim = (u8*)(csucc + cmax);
-  const u32 fmax = d.conn_frame_max[conn];
+  const u32 fmax = hd.fmax;
   FS_MARK(15);
   const u8* const seg_C = d.carry + (u64)conn * d.carry_cap;
-  const u8* const seg_N = (const u8*)d.in->ingress + d.segs[s].src;
+  const u8* const seg_N = (const u8*)d.in->ingress + src;
   // the common segment is copied into the work buffer by the screen pass itself: one read
   // of the sources, the work copy, the LDS stage and the candidate mask from the same
   // registers (was: a copy pass, then the screen re-reading the copy)
@@ -895,12 +908,65 @@ DEV void frame_scan_seg(const DS& d, const u32 s) {
 #undef CPOS
 }
 
+// the step's ingress payload copy, queued by the host on one or two SDMA engines through HSA
+// (Engine h2d_hsa): waited for here, on the device, by the kernel that first reads the slot.
+// No marker on a HIP stream and no cross-queue barrier sits between two steps' copies, so
+// they run back to back on their engine (bench/micro/h2d_chain_probe.hip, profiles/r6_z).
+// Block 0 alone polls the completion signals -- they live in host memory, every poll is a
+// read over the link the copy is using -- and passes the news on through a device word
+// (tot[TS_H2D_SEEN] = step + 1) the other blocks poll at agent scope.  The SDMA engine
+// writes HBM behind the L2s: every block of the grid, with a segment or without, ends its
+// wait with a system-scope acquire before it reads the slot or returns, so every XCD the
+// dispatcher gave a block has dropped its stale lines of the slot before k_decode,
+// k_route_store and the later readers run -- as the 16 blocks of the earlier k_h2d_wait did,
+// with a block per CU instead of two per XCD.
+// Bounded: a copy that never completes lets the step run on (block 0 passes the word on
+// when its budget is spent, and every other block has the same budget), and the host's
+// check of the signal at collection (Engine::wait_results) reports it
+DEV void h2d_wait(const DS& d) {
+  const u64 sig = d.in->h2d_sig, sig2 = d.in->h2d_sig2;   // (sig2: a payload split over two engines)
+  if (!sig) return;
+  const u32 lim = d.in->h2d_polls ? d.in->h2d_polls : (1u << 24);
+  const u32 seen = (u32)d.in->step + 1u;
+  // (one wave polls and acquires: the block's waves share the CU's L1 and the XCD's L2, and
+  // the barrier keeps their reads of the slot behind it)
+  if (threadIdx.x < 64) {
+    if (threadIdx.x != 0) {
+    } else if (blockIdx.x == 0) {
+      for (u32 it = 0; it < lim; ++it) {
+        if (__hip_atomic_load((const i64*)sig, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0 &&
+            (!sig2 || __hip_atomic_load((const i64*)sig2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0))
+          break;
+        __builtin_amdgcn_s_sleep(4);
+      }
+      __hip_atomic_store(&d.tot[TS_H2D_SEEN], seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      for (u32 it = 0; it < lim; ++it) {
+        if (__hip_atomic_load(&d.tot[TS_H2D_SEEN], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == seen) break;
+        __builtin_amdgcn_s_sleep(4);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  }
+  __syncthreads();
+}
+
+// the same wait as a launch of its own, 16 blocks in front of the frame scan: for a frame
+// scan grid of fewer blocks than that (a small seg_max), which could not reach every XCD
+__global__ __launch_bounds__(64) void k_h2d_wait(DS d) { h2d_wait(d); }
+
 // block-stride over the segments: the grid is capped below seg_max (a 1024-thread block
-// per segment slot of the capacity would mostly launch idle waves)
-__global__ __launch_bounds__(FS_NT) void k_frame_scan(DS d) {
+// per segment slot of the capacity would mostly launch idle waves).  wait: every block waits
+// for the step's payload (h2d_wait) -- one with a segment loads its first descriptor before
+// it does -- so a step never ends before its copy, whatever its segments
+__global__ __launch_bounds__(FS_NT) void k_frame_scan(DS d, u32 wait) {
   const u32 nseg = d.in->nseg;
+  if (!wait && blockIdx.x >= nseg) return;
+  FsHead hd{};
+  if (blockIdx.x < nseg) hd = fs_head(d, blockIdx.x);
+  if (wait) h2d_wait(d);
   for (u32 s = blockIdx.x; s < nseg; s += gridDim.x) {
-    frame_scan_seg(d, s);
+    frame_scan_seg(d, s, s == blockIdx.x ? hd : fs_head(d, s));
     __syncthreads();   // the next segment reuses the LDS
   }
 }

@@ -62,7 +62,8 @@ enum : u32 {
   TS_NDGET = 69,                        // Basic.Get commands the frame scan decoded (DGet list)
   TS_SPILL_USED = 70,                   // bytes of StepIn.spill_budget reserved this step (k_dequeue)
   TS_DQ_TICKET = 71,                    // k_dequeue finished-block ticket (last block: the step's runs)
-  TS_HOP_N = 72                         // hop_q entries reserved this step (exchange-to-exchange walks)
+  TS_HOP_N = 72,                        // hop_q entries reserved this step (exchange-to-exchange walks)
+  TS_H2D_SEEN = 73                      // (u32)StepIn.step + 1 once block 0 of the ingress wait saw the copy done
 };
 
 // Basic.Get decoded from a connection's bytes by the frame scan (no host round trip): served

@@ -100,7 +100,7 @@ struct StepSlot {
   u32 nget = 0, nunp = 0;          // Basic.Gets / unpauses it carried
   u32 dl_step = 0;                 // delta bytes it carried
   bool h2d_hip = true;             // its stream waits for ev_h2d
-  u64 h2d_addr = 0, h2d_addr2 = 0; // the words its k_h2d_wait polled (0: none; second half of a split payload)
+  u64 h2d_addr = 0, h2d_addr2 = 0; // the words its frame scan's wait polled (0: none; second half of a split payload)
   bool eager_d2h = false;          // its egress copy was queued at launch (copy_mode 2)
   // a payload queued ahead of its submit (prefetch)
   bool pre = false;
@@ -286,7 +286,7 @@ class Engine {
     sdma_pref_ = cfg.contains("sdma_engine") ? cfg["sdma_engine"].cast<int>() : -1;
     // (measured: no step-period gain in bench.py, 45.9 / 46.4 vs 45.9 / 46.3 M msgs/s,
     // profiles/r6_sp/ -- the egress D2H shares the link; opt-in)
-    h2d_split_cfg_ = get("h2d_split", 0) != 0;
+    h2d_split_cfg_ = get("h2d_split", 1) != 0;         // (on unless explicitly 0: with h2d_hsa, payloads >= h2d_split_min)
     h2d_split_min_ = get("h2d_split_min", 4u << 20);   // (tests lower it: every payload splits)
     wait_ms_ = (u32)get("wait_timeout_ms", 10000);
     sdma_split_ = cfg.contains("sdma_split") ? std::max(1, std::min(2, cfg["sdma_split"].cast<int>())) : 1;
@@ -703,7 +703,7 @@ class Engine {
     if (d_.world == 1 && get("overlap", 1) == 0 && get("h2d_alt", 0) != 0)
       HIPCHECK(hipStreamCreateWithFlags(&s_h2d_alt_, hipStreamNonBlocking));
     // (non-overlapped single GPU, HSA egress, cfg h2d_hsa) ingress payloads queued on an SDMA
-    // engine through HSA and waited for on the device (k_h2d_wait): consecutive steps' copies
+    // engine through HSA and waited for on the device (k_frame_scan's h2d_wait): consecutive steps' copies
     // run back to back, with no HIP marker / cross-queue barrier between them
     h2d_hsa_ = copy_mode_ == 3 && !sdma_ && d_.world == 1 && get("overlap", 1) == 0 && get("h2d_hsa", 0) != 0;
     if (h2d_hsa_)
@@ -937,6 +937,8 @@ class Engine {
     o["sdma_engine2"] = engine_no(true, (u32)sdma_engine2_);
     o["h2d_hsa_engine"] = engine_no(h2d_hsa_, (u32)ing_engine_);
     o["h2d_hsa_engine2"] = engine_no(h2d_hsa_, (u32)ing_engine2_);
+    o["egress_tail_engine"] = engine_no(copy_mode_ == 3, (u32)tail_engine_);
+    o["h2d_split_min"] = h2d_split_min_;
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
     o["restore_max"] = restore_max_;
     o["xfer_desc_max"] = d_.xfer_desc_max; o["xfer_bytes"] = d_.xfer_bytes; o["world_max"] = WORLD_MAX;
@@ -968,8 +970,11 @@ class Engine {
   int sdma_pref_ = -1, sdma_split_ = 1;
   bool gated_ = false;     // egress D2H queued at launch behind a gate (HSA SDMA)
   bool h2d_hsa_ = false;   // ingress payloads in GPU-mapped host memory go to an SDMA engine through HSA
-  bool h2d_split_cfg_ = false;
+  bool h2d_split_cfg_ = true;
   u64 h2d_split_min_ = 4u << 20;
+  // payload copies so far: in two halves on two engines, whole on the ingress engine, by the
+  // runtime (pageable memory / h2d_hsa off) -- a split that silently does not happen shows here
+  u64 h2d_n_[3] = {0, 0, 0};
   u32 wait_ms_ = 10000;    // bounded_wait deadline
   int ref_back_ = -1;      // egress by reference: steps back a body may be referenced (-1 off)
   u32 ref_min_ = 256;      // smallest referenced body (smaller ones are cheaper inline)
@@ -1253,7 +1258,7 @@ class Engine {
     return a.type == hipMemoryTypeHost && a.devicePointer ? (u64)a.devicePointer : 0;
   }
 
-  // a step's payload into ingress slot is: on the HSA path (k_h2d_wait waits for it on the
+  // a step's payload into ingress slot is: on the HSA path (k_frame_scan waits for it on the
   // device) or as a runtime copy on stream ps (the step's stream waits for ev_h2d_)
   void ingress_copy(u64 step, int is, u64 ptr, u64 len, hipStream_t ps) {
     IngressSlot& ig = ing_[is];
@@ -1282,8 +1287,10 @@ class Engine {
       }
       ig.hsa = true;
       ig.split = split;
+      ++h2d_n_[split ? 0 : 1];
       return;
     }
+    ++h2d_n_[2];
     if (step >= INGRESS_SLOTS && ig.read_issued && hipEventQuery(ig.ev_read) != hipSuccess)
       HIPCHECK(hipStreamWaitEvent(ps, ig.ev_read, 0));
     HIPCHECK(hipMemcpyAsync((void*)ig.buf, (const void*)ptr, len,
@@ -1473,7 +1480,7 @@ class Engine {
     if (sp.staged) throw std::runtime_error("wait_results: step staged but never launched");
     HIPCHECK(hipEventSynchronize(sp.ev_done));
     sp.inflight = false;
-    if (sp.h2d_addr) {   // (k_h2d_wait gives up after its poll budget: the step then ran on a stale slot)
+    if (sp.h2d_addr) {   // (the device-side wait gives up after its poll budget: the step then ran on a stale slot)
       if (*(volatile const i64*)sp.h2d_addr != 0 || (sp.h2d_addr2 && *(volatile const i64*)sp.h2d_addr2 != 0)) {
         wait_failed_ = true;
         throw std::runtime_error("ingress copy of step " + std::to_string(sp.launch_seq) +
@@ -1503,6 +1510,16 @@ class Engine {
                                    "egress_copy", "egress_wait", "exchange", "exchange_counts", "exchange_thread"};
     py::dict o;
     for (int i = 0; i < 9; ++i) { o[names[i]] = ht_[i]; if (reset) ht_[i] = 0; }
+    return o;
+  }
+
+  // payload copies since construction, by path (a payload that should split and does not is
+  // counted unsplit), and the engines the HSA path uses (-1: none)
+  py::dict h2d_stats() const {
+    py::dict o;
+    o["split"] = h2d_n_[0]; o["unsplit"] = h2d_n_[1]; o["runtime"] = h2d_n_[2];
+    o["engine"] = h2d_hsa_ && ing_engine_ ? __builtin_ctz((u32)ing_engine_) : -1;
+    o["engine2"] = h2d_hsa_ && ing_engine2_ ? __builtin_ctz((u32)ing_engine2_) : -1;
     return o;
   }
 
@@ -1768,16 +1785,26 @@ class Engine {
         break;
       }
     if (!ing_engine_) ing_engine_ = tail_engine_;
-    // a split payload's second engine (cfg h2d_split, default off): another full-rate one the
-    // egress does not use
+    // a split payload's second engine (cfg h2d_split, on unless 0): another full-rate one
+    // (0-3) that no egress copy uses -- on MI355X with the defaults engine 3, next to egress 1,
+    // tail 2, ingress 0.  When none is free next to the tail engine, the second half shares
+    // the tail engine's queue: the tail is an un-gated copy the host issues after the step
+    // (egress_copy) and an ingress half depends on nothing, so each can only wait for the
+    // other's bytes to move (at most half a payload), never for a gate.  The gated engines
+    // (sdma_engine_, sdma_engine2_) are never taken: a copy queued there sits behind a gated
+    // copy until the step in flight ends, and the step would wait for its own payload
     ing_engine2_ = (hsa_amd_sdma_engine_id_t)0;
-    if (h2d_split_cfg_)
-      for (u32 c : {3u, 2u})
+    if (h2d_split_cfg_) {
+      for (u32 c : {3u, 2u, 0u})
         if (((mask >> c) & 1u) && (1u << c) != (u32)ing_engine_ && (1u << c) != (u32)sdma_engine_ &&
             (1u << c) != (u32)sdma_engine2_ && (1u << c) != (u32)tail_engine_) {
           ing_engine2_ = (hsa_amd_sdma_engine_id_t)(1u << c);
           break;
         }
+      if (!ing_engine2_ && tail_engine_ != sdma_engine_ && tail_engine_ != sdma_engine2_ && tail_engine_ != ing_engine_ &&
+          __builtin_ctz((u32)tail_engine_) < 4)
+        ing_engine2_ = tail_engine_;
+    }
     for (EgressSlot& es : eg_)
       if (hsa_signal_create(0, 0, nullptr, &es.sdma_sig) != HSA_STATUS_SUCCESS ||
           hsa_signal_create(0, 0, nullptr, &es.tail_sig) != HSA_STATUS_SUCCESS ||
@@ -2699,11 +2726,16 @@ class Engine {
   void launch_ingest(hipStream_t s, const DS& d) {
     Range rg("chanamq.K1-K4.ingest");
     hipLaunchKernelGGL(k_stage, dim3(1), dim3(1024), 0, s, d);
-    if (h2d_hsa_) hipLaunchKernelGGL(k_h2d_wait, dim3(16), dim3(64), 0, s, d);
+    // the wait for the payload copy rides the frame scan's own blocks (every block of the
+    // grid waits and acquires, so every XCD a block lands on has dropped its stale lines of
+    // the slot); a grid too small to reach every XCD gets the wait as 16 blocks of its own
+    const dim3 fs_grid = capped(d.seg_max, n_cu_);
+    const bool fold = h2d_hsa_ && fs_grid.x >= 16;
+    if (h2d_hsa_ && !fold) hipLaunchKernelGGL(k_h2d_wait, dim3(16), dim3(64), 0, s, d);
     // one block per CU fits (154 KB of LDS): more blocks than CUs only queue behind the
     // busy ones, and blocks past the step's segments would still be dispatched one by one
     // after them (the grid is sized for capacity at capture)
-    hipLaunchKernelGGL(k_frame_scan, capped(d.seg_max, n_cu_), dim3(FS_NT), 0, s, d);
+    hipLaunchKernelGGL(k_frame_scan, fs_grid, dim3(FS_NT), 0, s, d, fold ? 1u : 0u);
     if (d.rank_scan)
       launch_scan(s, d, {{d.cmd_is_pub, d.cmd_pub_rank}, {d.cmd_is_ack, d.cmd_ack_rank}}, &d.ctr->n_cmds,
                   d.cmd_max, TS_CMD_PUBS, nullptr, /*ingest=*/true);
@@ -2909,6 +2941,7 @@ PYBIND11_MODULE(_dataplane, m) {
       .def("side_pending", &Engine::side_pending)
       .def("basic_get", &Engine::basic_get, py::arg("q"), py::arg("chslot"), py::arg("noack"), py::arg("now_ms"))
       .def("wait_results", &Engine::wait_results)
+      .def("h2d_stats", &Engine::h2d_stats)
       .def("egress_copy", &Engine::egress_copy)
       .def("egress_wait", &Engine::egress_wait)
       .def("egress_slot", &Engine::egress_slot)
