@@ -2156,8 +2156,8 @@ DEV void wave_consumed(const DS& d, u32 msg, u32 q, u64 qpos, u32 kind, bool val
 // window head over the contiguous run of finished slots, 256 slots per iteration
 #define MS_MAX 256   // multiple settles per channel per step resolved exactly (more: folded)
 struct MsLds {
-  u64 up[MS_MAX];
-  u32 rq[MS_MAX];
+  u64 up[MS_MAX + 1];   // (+ 1: the fold of the settles past MS_MAX)
+  u32 rq[MS_MAX + 1];
   u32 wc[4];
   u32 rc[4];     // store records per wave of the current chunk
   u32 rbase;     // their block reservation (INVALID: budget exhausted)
@@ -2213,7 +2213,7 @@ DEV void collect_settles(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, MsLds& m
       if (ms.up[k] > top) { ms.up[nb] = ms.up[k]; ms.rq[nb] = ms.rq[k]; ++nb; top = ms.up[k]; }
     const u64 oa = ms.ovf_a, orq = ms.ovf_r;   // past MS_MAX: the larger cover, appended
     const u64 om = oa > orq ? oa : orq;
-    if (om > top && nb < MS_MAX) { ms.up[nb] = om; ms.rq[nb] = orq > oa; ++nb; }
+    if (om > top) { ms.up[nb] = om; ms.rq[nb] = orq > oa; ++nb; }
     ms.nb = nb;
     d.ch_mlo[ch] = INVALID;
     d.ch_mhi[ch] = 0;
@@ -4002,32 +4002,44 @@ __global__ void k_side_out(const ColdRec* recs, const u32* cnt, u32 max_n, u32* 
 // ============================================================================ requeue (pre-step)
 // run by k_dequeue (fused k_requeue): the block of a queue with requeued items gathers
 // them, bitonic-sorts by queue position and pushes them back in front of the head with
-// the redelivered flag (QueueEntity.scala:415-446); the last block compacts the rest
-DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p) {
-  u32& cnt = *cnt_p;
-  u32 tid = threadIdx.x;
-  if (tid == 0) cnt = 0;
+// the redelivered flag (QueueEntity.scala:415-446); the last block compacts the rest.
+// The sort holds REQ_BLK items: a queue with more of them in one step is pushed in passes
+// over ranges of queue position, the highest range first (next to the head), so the
+// queue's order holds for any count up to req_max.
+
+// this queue's listed items with lo <= qpos < hi, counted; with `keep` the first REQ_BLK
+// of them (in arrival order) are gathered into kpos / kidx
+DEV u32 requeue_gather(const DS& d, u32 q, u32 n, u64 lo, u64 hi, bool keep, u64* kpos, u32* kidx, u32* cnt_p) {
+  const u32 tid = threadIdx.x;
+  if (tid == 0) *cnt_p = 0;
   __syncthreads();
-  u32 n = *d.req_n;
-  if (n > d.req_max) n = d.req_max;
   for (u32 i = tid; i < n; i += 256) {
-    if (d.req[i].q == q) {
-      u32 k = atomicAdd(&cnt, 1u);
-      if (k < REQ_BLK) { kpos[k] = d.req[i].qpos; kidx[k] = i; }
-    }
+    if (d.req[i].q != q) continue;
+    const u64 p = d.req[i].qpos;
+    if (p < lo || p >= hi) continue;
+    const u32 k = atomicAdd(cnt_p, 1u);
+    if (keep && k < REQ_BLK) { kpos[k] = p; kidx[k] = i; }
   }
   __syncthreads();
-  u32 m = cnt < REQ_BLK ? cnt : REQ_BLK;
+  const u32 c = *cnt_p;
+  __syncthreads();
+  return c;
+}
+
+// the m gathered items sorted by queue position; the first k of them written to ring
+// positions base, base + 1, .. and taken off the list
+DEV void requeue_sort_push(const DS& d, u32 q, u64* kpos, u32* kidx, u32 m, u32 k, u64 base, u64 mask) {
+  const u32 tid = threadIdx.x;
   u32 np2 = 1;
   while (np2 < m) np2 <<= 1;
   for (u32 i = m + tid; i < np2; i += 256) { kpos[i] = ~0ull; kidx[i] = INVALID; }
   __syncthreads();
-  for (u32 k = 2; k <= np2; k <<= 1) {
-    for (u32 j = k >> 1; j > 0; j >>= 1) {
+  for (u32 sz = 2; sz <= np2; sz <<= 1) {
+    for (u32 j = sz >> 1; j > 0; j >>= 1) {
       for (u32 i = tid; i < np2; i += 256) {
         u32 ij = i ^ j;
         if (ij > i) {
-          bool up = (i & k) == 0;
+          bool up = (i & sz) == 0;
           if ((kpos[i] > kpos[ij]) == up) {
             u64 t = kpos[i]; kpos[i] = kpos[ij]; kpos[ij] = t;
             u32 x = kidx[i]; kidx[i] = kidx[ij]; kidx[ij] = x;
@@ -4037,24 +4049,76 @@ DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p) {
       __syncthreads();
     }
   }
-  u64 head = d.q_head[q], tail = d.q_tail[q];
-  u64 mask = d.q_ring_mask[q];
-  u64 freec = mask + 1 - (tail - head);
-  u32 k = m < freec ? m : (u32)freec;
   for (u32 i = tid; i < k; i += 256) {
     const ReqItem r = d.req[kidx[i]];
     Desc ds;
     ds.msg = r.msg;
     ds.flags = 1;
     ds.expire_ms = r.expire_ms;
-    d.ring[d.q_ring_off[q] + ((head - k + i) & mask)] = ds;
+    d.ring[d.q_ring_off[q] + ((base + i) & mask)] = ds;
     // consumed (agent-coherent: the compacting block of another XCD reads it after the ticket)
     __hip_atomic_store(&d.req[kidx[i]].q, INVALID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
+}
+
+DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p) {
+  const u32 tid = threadIdx.x;
+  u32 n = *d.req_n;
+  if (n > d.req_max) n = d.req_max;
+  const u64 head = d.q_head[q], tail = d.q_tail[q];
+  const u64 mask = d.q_ring_mask[q];
+  const u64 freec = mask + 1 - (tail - head);
+  const u32 total = requeue_gather(d, q, n, 0, ~0ull, true, kpos, kidx, cnt_p);
+  u32 done = 0;
+  if (total <= REQ_BLK) {
+    done = total < freec ? total : (u32)freec;   // (no room for all: the lowest positions)
+    requeue_sort_push(d, q, kpos, kidx, total, done, head - done, mask);
+  } else {
+    // the positions' bounds (kpos[0..1] as scratch: the gathers below rewrite them)
+    if (tid == 0) { kpos[0] = ~0ull; kpos[1] = 0; }
+    __syncthreads();
+    for (u32 i = tid; i < n; i += 256) {
+      if (d.req[i].q != q) continue;
+      atomicMin((unsigned long long*)&kpos[0], (unsigned long long)d.req[i].qpos);
+      atomicMax((unsigned long long*)&kpos[1], (unsigned long long)d.req[i].qpos);
+    }
+    __syncthreads();
+    const u64 lo0 = kpos[0];
+    u64 hi = kpos[1] + 1;
+    __syncthreads();
+    if (total > freec) {   // no room for all: the items below the largest bound that fits
+      u64 g = lo0, b = hi;   // count[lo0, g) <= freec < count[lo0, b)
+      while (b - g > 1) {
+        const u64 mid = g + (b - g) / 2;
+        if (requeue_gather(d, q, n, lo0, mid, false, kpos, kidx, cnt_p) <= freec) g = mid;
+        else b = mid;
+      }
+      hi = g;
+    }
+    // passes from the head downwards: the widest range [lo, hi) of at most REQ_BLK items
+    // (bisected by count); every loop condition is block-uniform
+    while (hi > lo0) {
+      u64 lo = lo0;
+      if (requeue_gather(d, q, n, lo, hi, false, kpos, kidx, cnt_p) > REQ_BLK) {
+        u64 b = lo0, g = hi;   // count[g, hi) <= REQ_BLK < count[b, hi)
+        while (g - b > 1) {
+          const u64 mid = b + (g - b) / 2;
+          if (requeue_gather(d, q, n, mid, hi, false, kpos, kidx, cnt_p) <= REQ_BLK) g = mid;
+          else b = mid;
+        }
+        lo = g;
+      }
+      if (lo == hi) break;   // more than REQ_BLK items at one position: they stay listed
+      const u32 m = requeue_gather(d, q, n, lo, hi, true, kpos, kidx, cnt_p);
+      requeue_sort_push(d, q, kpos, kidx, m, m, head - done - m, mask);
+      done += m;
+      hi = lo;
+    }
+  }
   if (tid == 0) {
-    d.q_head[q] = head - k;
-    d.req_q_n[q] -= k;
+    d.q_head[q] = head - done;
+    d.req_q_n[q] -= done;
   }
 }
 
