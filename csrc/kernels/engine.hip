@@ -27,8 +27,11 @@
 
 #include "dataplane.hip"
 #include "delta_stage.h"
+#include "sdma_plan.h"
+#include "side_box.h"
 #include "xchg_host.h"
 #include "xchg_rccl.h"
+#include "xchg_worker.h"
 
 namespace py = pybind11;
 
@@ -1053,23 +1056,14 @@ class Engine {
   u64 xseq_ = 0;
   // asynchronous exchange (xchg_setup async=true): one job at a time on the exchange thread
   bool async_x_ = false;
-  std::thread xth_;
-  std::mutex xmu_;
-  std::condition_variable xcv_;
-  bool xstop_ = false, xjob_ = false, xbusy_ = false, xres_ = false;
-  int xq_ = 0, xres_rc_ = 0;
-  u32 xflags_ = 0, xres_orf_ = 0, xjob_seq_ = 0, xseq_job_ = 0;
-  std::string xerr_;
+  XchgWorker xw_;
   u32* xflag_h_ = nullptr;           // host-mapped [0] last finished job, [1] a device wait gave up
   u32* xflag_d_ = nullptr;
   std::mutex cap_mu_;                // graph captures vs the exchange thread's HIP calls
   hipStream_t s_x_ = nullptr;        // the shared-memory exchange's copies
   // ---- side operations, table IO
   static constexpr u32 COLD_BATCH = 1u << 16;   // cold records per pick / scan call
-  struct Side { int kind; u32 a; u64 b, c; u32 max_n; u64 max_bytes; u32 n; bool launched; };
-  Side side_{SIDE_NONE, 0, 0, 0, 0, 0, 0, false};
-  std::mutex side_mu_;
-  std::condition_variable side_cv_;
+  SideBox side_;
   hipEvent_t ev_side_ = nullptr;
   void* side_h_ = nullptr;      // host-mapped: [count @0][ColdRec[] @64]
   void* side_d_ = nullptr;
@@ -1162,7 +1156,7 @@ class Engine {
     // the slot's previous D2H (step t - EGRESS_SLOTS, long finished) must be complete before
     // its gate is re-armed and its buffer rendered into again
     if (copy_mode_ == 3 && (es.sdma_pending || es.tail_pending)) { HostTimer t(&ht_[1]); sdma_wait(e); }
-    es.spec = gated_ ? spec_bytes() : 0;
+    es.spec = gated_ ? spec_bytes(eg_hist_, egress_alloc_) : 0;
     in->gate = 0;
     if (es.spec) {
       hsa_signal_store_screlease(es.gate_sig, 1);
@@ -1270,10 +1264,8 @@ class Engine {
         HIPCHECK(hipEventSynchronize(ig.ev_read));
       if (ig.hsa) bounded_wait(ig.sig, -1, "ingress H2D");
       if (ig.split) bounded_wait(ig.sig2, -1, "ingress H2D");
-      // a large payload in two halves on two engines at once: 56.8 vs 54.9 GB/s on one (the
-      // PCIe link is the bound, bench/micro/h2d_chain_probe.hip, profiles/r6_z/h2d_chain3.txt)
-      const bool split = ing_engine2_ && len >= h2d_split_min_ && len > 8192;
-      const u64 h1 = split ? ((len / 2 + 4095) & ~u64(4095)) : len;
+      const u64 h1 = ingress_cut(len, h2d_split_min_, ing_engine2_ != 0);
+      const bool split = h1 < len;
       hsa_signal_store_relaxed(ig.sig, 1);
       if (hsa_amd_memory_async_copy_on_engine(ig.buf, gpu_agent_, (const void*)src, cpu_agent_, h1, 0,
                                               nullptr, ig.sig, ing_engine_, true) != HSA_STATUS_SUCCESS)
@@ -1343,7 +1335,7 @@ class Engine {
     dl_.deltas_pending(&nrec, &nbytes, &nd);
     return py::make_tuple(nrec, nbytes, nd);
   }
-  bool host_work() { return dl_.host_work() || side_queued(); }
+  bool host_work() { return dl_.host_work() || side_.queued(); }
   // from the next submitted step on, every step moves queued bodies in the oldest frac/65536
   // of the HBM log (past the first `hot` entries of a queue with consumers) to the host
   // spill ring, at most `budget` bytes a step -- spill() without the pipeline drain; frac 0
@@ -1383,7 +1375,7 @@ class Engine {
       // (the routing half of step t-2); the routing half on s_comp_ behind it and behind
       // the previous step's routing half (stream order), as a single step would run
       // a side operation between the previous step's routing half and this step's ingest
-      if (side_queued()) {
+      if (side_.queued()) {
         run_side(s_comp_);
         HIPCHECK(hipStreamWaitEvent(s_ing_, ev_side_, 0));
       }
@@ -1574,15 +1566,7 @@ class Engine {
       // slot's signal once (measured slower on MI355X: 28.9 vs 38.6 M msgs/s, p99 6.6 ms,
       // profiles/r4_sdma_split.md -- off by default)
       const int k = (n >= (2u << 20) && sdma_engine2_) ? 2 : 1;
-      hsa_signal_store_screlease(es.sdma_sig, k);
-      const u64 half = k == 2 ? ((n / 2) & ~(u64)4095) : n;
-      for (int i = 0; i < k; ++i) {
-        const u64 off = i ? half : 0, len = i ? n - half : half;
-        hsa_status_t st = hsa_amd_memory_async_copy_on_engine(
-            (u8*)es.host + off, cpu_agent_, (u8*)es.dev + off, gpu_agent_, len, 0, nullptr,
-            es.sdma_sig, i ? sdma_engine2_ : sdma_engine_, true);
-        if (st != HSA_STATUS_SUCCESS) throw std::runtime_error("hsa_amd_memory_async_copy_on_engine failed");
-      }
+      if (!sdma_d2h(es, n, k, false)) throw std::runtime_error("hsa_amd_memory_async_copy_on_engine failed");
       es.sdma_pending = true;
       return n;
     }
@@ -1599,12 +1583,33 @@ class Engine {
 
   void egress_wait(int p) { egress_wait_slot(par(p).slot); }
 
-  // the slot's D2H (+ its tail) complete
-  void sdma_wait(int e) {
+  // the slot's SDMA D2H (+ its tail) landed.  Reads the pending flags and leaves them as they
+  // are: egress_ready runs on another thread than the stepper and must not write them; the
+  // stepper's waits (sdma_wait, egress_wait_slot) clear them afterwards
+  void sdma_landed(int e) {
     EgressSlot& es = eg_[e];
     if (es.sdma_pending) bounded_wait(es.sdma_sig, e, "egress D2H");
     if (es.tail_pending) bounded_wait(es.tail_sig, e, "egress tail D2H");
-    es.sdma_pending = es.tail_pending = false;
+  }
+  void sdma_wait(int e) {
+    sdma_landed(e);
+    eg_[e].sdma_pending = eg_[e].tail_pending = false;
+  }
+
+  // n bytes of egress slot es to the host on k SDMA engines, each part decrementing the slot's
+  // completion signal once; gated: every part starts when the slot's gate opens.  false: the
+  // runtime refused a part
+  bool sdma_d2h(EgressSlot& es, u64 n, int k, bool gated) {
+    hsa_signal_store_screlease(es.sdma_sig, k);
+    const u64 half = egress_cut(n, k);
+    for (int i = 0; i < k; ++i) {
+      const u64 off = i ? half : 0, len = i ? n - half : half;
+      if (hsa_amd_memory_async_copy_on_engine((u8*)es.host + off, cpu_agent_, (u8*)es.dev + off, gpu_agent_, len,
+                                              gated ? 1 : 0, gated ? &es.gate_sig : nullptr, es.sdma_sig,
+                                              i ? sdma_engine2_ : sdma_engine_, true) != HSA_STATUS_SUCCESS)
+        return false;
+    }
+    return true;
   }
 
   // a copy's completion signal reaching 0: an active spin first (a step's egress lands
@@ -1633,15 +1638,6 @@ class Engine {
   void inject_h2d_fault() { h2d_fault_ = true; }
   bool wait_failed() const { return wait_failed_; }
 
-  // gated egress: bytes to copy speculatively for the next step -- the largest of the last
-  // four steps' egress + 1/16 + 64 KB, in 64 KB units (0 after four steps without egress)
-  u64 spec_bytes() const {
-    u64 mx = 0;
-    for (u64 v : eg_hist_) mx = v > mx ? v : mx;
-    if (!mx) return 0;
-    const u64 sz = (mx + mx / 16 + (64u << 10) + 65535) & ~(u64)65535;
-    return sz < egress_alloc_ ? sz : egress_alloc_;
-  }
   // gated egress counters: [gated copies, tail copies, bytes copied speculatively, bytes rendered]
   py::dict egress_stats() const {
     py::dict o;
@@ -1672,19 +1668,14 @@ class Engine {
   // egress_wait_slot without touching engine state (any thread; the slot's D2H was
   // issued before the caller learnt of the slot)
   void egress_ready(int e) {
-    EgressSlot& es = eg_[e];
-    if (copy_mode_ == 3) {
-      if (es.sdma_pending) bounded_wait(es.sdma_sig, e, "egress D2H");
-      if (es.tail_pending) bounded_wait(es.tail_sig, e, "egress tail D2H");
-      return;
-    }
-    if (es.d2h_issued) HIPCHECK(hipEventSynchronize(es.ev_d2h));
+    if (copy_mode_ == 3) { sdma_landed(e); return; }
+    if (eg_[e].d2h_issued) HIPCHECK(hipEventSynchronize(eg_[e].ev_d2h));
   }
 
   void egress_wait_slot(int e) {
     HostTimer ht(&ht_[5]);
-    if (copy_mode_ == 3) { sdma_wait(e); return; }
-    if (eg_[e].d2h_issued) HIPCHECK(hipEventSynchronize(eg_[e].ev_d2h));
+    egress_ready(e);
+    if (copy_mode_ == 3) eg_[e].sdma_pending = eg_[e].tail_pending = false;
   }
 
   // the egress D2H of slot e, queued now: starts when the step's last kernel opens the gate
@@ -1696,18 +1687,9 @@ class Engine {
     // the same gate, each decrementing the slot's completion signal once
     const u64 n = es.spec;
     const int k = (sdma_split_ > 1 && sdma_engine2_ && n >= (4u << 20)) ? 2 : 1;
-    const u64 half = k == 2 ? ((n / 2) & ~(u64)4095) : n;
-    hsa_signal_store_screlease(es.sdma_sig, k);
-    for (int i = 0; i < k; ++i) {
-      const u64 off = i ? half : 0, len = i ? n - half : half;
-      hsa_status_t st = hsa_amd_memory_async_copy_on_engine((u8*)es.host + off, cpu_agent_,
-                                                            (u8*)es.dev + off, gpu_agent_, len, 1,
-                                                            &es.gate_sig, es.sdma_sig,
-                                                            i ? sdma_engine2_ : sdma_engine_, true);
-      if (st != HSA_STATUS_SUCCESS) {
-        hsa_signal_store_screlease(es.sdma_sig, 0);
-        throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (gated egress) failed");
-      }
+    if (!sdma_d2h(es, n, k, true)) {
+      hsa_signal_store_screlease(es.sdma_sig, 0);
+      throw std::runtime_error("hsa_amd_memory_async_copy_on_engine (gated egress) failed");
     }
     es.sdma_pending = true;
     ++eg_stats_[0];
@@ -1750,61 +1732,14 @@ class Engine {
     uint32_t mask = 0;
     if (hsa_amd_memory_copy_engine_status(cpu_agent_, gpu_agent_, &mask) != HSA_STATUS_SUCCESS || !mask)
       throw std::runtime_error("no SDMA engine available for device -> host copies");
-    // not the engine of the runtime's own H2D copies: one SDMA engine serialises both
-    // directions (measured 54 GB/s total vs 94 GB/s on two engines, bench/pcie_probe.hip)
-    // (measured on MI355X: engines 0-3 reach PCIe rate, 8 and 15 a third of it)
-    u32 pick = 0;
-    if (sdma_pref_ >= 0 && (mask >> sdma_pref_) & 1u) pick = (u32)sdma_pref_;
-    else if ((mask >> 1) & 1u) pick = 1;
-    else while (!((mask >> pick) & 1u)) ++pick;
-    sdma_engine_ = (hsa_amd_sdma_engine_id_t)(1u << pick);
-    // a second engine for split egress copies: another full-rate one (0-3), not engine 0
-    // (the runtime's H2D engine) when there is a choice
-    sdma_engine2_ = (hsa_amd_sdma_engine_id_t)0;
-    if (sdma_split_ > 1)
-      for (u32 c : {2u, 3u, 0u})
-        if (c != pick && ((mask >> c) & 1u)) { sdma_engine2_ = (hsa_amd_sdma_engine_id_t)(1u << c); break; }
-    // the tail engine (gated egress): another full-rate engine than the gated copies' --
-    // which can sit behind the next step's gate -- and than the runtime's H2D engine 0
-    // (nor the split copies' second engine: an engine's queue is in order, and a gated copy
-    // waiting there for the next step's gate would hold the tail back by a step)
-    tail_engine_ = sdma_engine_;
-    for (u32 c : {2u, 3u, 0u})
-      if (c != pick && ((mask >> c) & 1u) && (1u << c) != (u32)sdma_engine2_) {
-        tail_engine_ = (hsa_amd_sdma_engine_id_t)(1u << c);
-        break;
-      }
-    // the ingress engine (cfg h2d_hsa): engine 0, the runtime's own H2D engine -- the egress
-    // engines stay free of it (measured: egress on engine 0 next to the ingress copies halves
-    // the throughput, profiles/r6_x); else any full-rate engine the egress does not use
-    ing_engine_ = (hsa_amd_sdma_engine_id_t)0;
-    for (u32 c : {0u, 3u, 2u, 1u})
-      if (((mask >> c) & 1u) && (1u << c) != (u32)sdma_engine_ && (1u << c) != (u32)sdma_engine2_ &&
-          (1u << c) != (u32)tail_engine_) {
-        ing_engine_ = (hsa_amd_sdma_engine_id_t)(1u << c);
-        break;
-      }
-    if (!ing_engine_) ing_engine_ = tail_engine_;
-    // a split payload's second engine (cfg h2d_split, on unless 0): another full-rate one
-    // (0-3) that no egress copy uses -- on MI355X with the defaults engine 3, next to egress 1,
-    // tail 2, ingress 0.  When none is free next to the tail engine, the second half shares
-    // the tail engine's queue: the tail is an un-gated copy the host issues after the step
-    // (egress_copy) and an ingress half depends on nothing, so each can only wait for the
-    // other's bytes to move (at most half a payload), never for a gate.  The gated engines
-    // (sdma_engine_, sdma_engine2_) are never taken: a copy queued there sits behind a gated
-    // copy until the step in flight ends, and the step would wait for its own payload
-    ing_engine2_ = (hsa_amd_sdma_engine_id_t)0;
-    if (h2d_split_cfg_) {
-      for (u32 c : {3u, 2u, 0u})
-        if (((mask >> c) & 1u) && (1u << c) != (u32)ing_engine_ && (1u << c) != (u32)sdma_engine_ &&
-            (1u << c) != (u32)sdma_engine2_ && (1u << c) != (u32)tail_engine_) {
-          ing_engine2_ = (hsa_amd_sdma_engine_id_t)(1u << c);
-          break;
-        }
-      if (!ing_engine2_ && tail_engine_ != sdma_engine_ && tail_engine_ != sdma_engine2_ && tail_engine_ != ing_engine_ &&
-          __builtin_ctz((u32)tail_engine_) < 4)
-        ing_engine2_ = tail_engine_;
-    }
+    // which engine carries what: sdma_plan.h (with the defaults on MI355X: egress 1, tail 2,
+    // ingress 0 and 3)
+    const SdmaPlan pl = plan_sdma(mask, sdma_pref_, sdma_split_, h2d_split_cfg_);
+    sdma_engine_ = (hsa_amd_sdma_engine_id_t)pl.egress;
+    sdma_engine2_ = (hsa_amd_sdma_engine_id_t)pl.egress2;
+    tail_engine_ = (hsa_amd_sdma_engine_id_t)pl.tail;
+    ing_engine_ = (hsa_amd_sdma_engine_id_t)pl.ingress;
+    ing_engine2_ = (hsa_amd_sdma_engine_id_t)pl.ingress2;
     for (EgressSlot& es : eg_)
       if (hsa_signal_create(0, 0, nullptr, &es.sdma_sig) != HSA_STATUS_SUCCESS ||
           hsa_signal_create(0, 0, nullptr, &es.tail_sig) != HSA_STATUS_SUCCESS ||
@@ -1967,8 +1902,9 @@ class Engine {
         xflag_d_ = (u32*)alloc("xflag", 64, true);
         xflag_h_ = (u32*)buf("xflag").ptr;
       }
-      __atomic_store_n(&xflag_h_[0], xjob_seq_, __ATOMIC_RELEASE);
-      xth_ = std::thread([this] { x_loop(); });
+      __atomic_store_n(&xflag_h_[0], xw_.last_seq(), __ATOMIC_RELEASE);
+      xw_.start([this](int q, u32 fl, u32 seq) { return x_run(q, fl, seq); },
+                [this] { HIPCHECK(hipSetDevice(device_)); });
     }
   }
 
@@ -2007,80 +1943,42 @@ class Engine {
     // counts parity q^1 held two steps ago.  (Its last reader, step t-2, has
     // finished: its results were collected before this step's submit)
     x_recv_counts(q ^ 1, nullptr);
-    std::lock_guard<std::mutex> g(xmu_);
-    xq_ = q;
-    xflags_ = flags;
-    xseq_job_ = ++xjob_seq_;
-    if (xseq_job_ == 0) xseq_job_ = ++xjob_seq_;   // (0: no wait)
-    par_[q ^ 1].b_wait = xseq_job_;
-    xjob_ = true;
-    xcv_.notify_all();
+    par_[q ^ 1].b_wait = xw_.post(q, flags);
     return 0;
   }
 
-  // the last job's result (waits for it); (0, 0) when none is uncollected
+  // the last job's result (waits for it); (0, 0) when none is uncollected.  A phase B that
+  // gave up is reported once the job in flight ended and ahead of its result (which stays)
   void x_collect(int* rc, u32* orf) {
-    std::unique_lock<std::mutex> g(xmu_);
-    xcv_.wait(g, [&] { return !xjob_ && !xbusy_; });
-    *rc = 0;
-    *orf = 0;
+    xw_.wait_idle();
     if (xflag_h_ && __atomic_load_n(&xflag_h_[1], __ATOMIC_ACQUIRE))
       throw std::runtime_error("a phase B gave up waiting for its exchange (exchange thread lost)");
-    if (xres_) {
-      *rc = xres_rc_;
-      *orf = xres_orf_;
-      xres_ = false;
-      if (xres_rc_ == -1) throw std::runtime_error("exchange thread: " + xerr_);
-    }
+    xw_.collect(rc, orf);
   }
 
-  void x_loop() {
-    HIPCHECK(hipSetDevice(device_));
-    std::unique_lock<std::mutex> g(xmu_);
-    while (true) {
-      xcv_.wait(g, [&] { return xstop_ || xjob_; });
-      if (!xjob_) return;
-      const int q = xq_;
-      const u32 fl = xflags_, seq = xseq_job_;
-      xjob_ = false;
-      xbusy_ = true;
-      g.unlock();
-      u32 orf = 0;
-      int rc;
-      std::string err;
-      try {
-        std::lock_guard<std::mutex> cg(cap_mu_);
-        rc = exchange_now(q, fl, &orf, q ^ 1);
-      } catch (const std::exception& e) {
-        rc = -1;
-        err = e.what();
-      }
-      if (rc) x_recv_counts(q ^ 1, nullptr);   // phase B imports nothing
-      __atomic_store_n(&xflag_h_[0], seq, __ATOMIC_RELEASE);
-      g.lock();
-      xbusy_ = false;
-      xres_ = true;
-      xres_rc_ = rc;
-      xres_orf_ = orf;
-      xerr_ = err;
-      xcv_.notify_all();
+  // one job of the exchange thread (xchg_worker.h: the order of what it publishes is the
+  // contract): the exchange of parity q's step into parity q^1's import words
+  XchgWorker::Result x_run(int q, u32 fl, u32 seq) {
+    XchgWorker::Result r;
+    try {
+      std::lock_guard<std::mutex> cg(cap_mu_);
+      r.rc = exchange_now(q, fl, &r.orf, q ^ 1);
+    } catch (const std::exception& e) {
+      r.rc = -1;
+      r.err = e.what();
     }
+    if (r.rc) x_recv_counts(q ^ 1, nullptr);   // phase B imports nothing
+    __atomic_store_n(&xflag_h_[0], seq, __ATOMIC_RELEASE);
+    return r;
   }
 
   // shutdown (abort true): a job still waiting for a peer gives up at once
   void x_stop(bool abort = false) {
-    {
-      std::lock_guard<std::mutex> g(xmu_);
-      xstop_ = true;
-      xcv_.notify_all();
-      if (abort && (xjob_ || xbusy_)) {
-        if (shm_) shm_->abort();
-        if (cshm_) cshm_->abort();
-      }
-    }
-    if (xth_.joinable()) xth_.join();
-    std::lock_guard<std::mutex> g(xmu_);
-    xstop_ = xjob_ = xbusy_ = xres_ = false;
+    if (abort) xw_.stop([this] {
+      if (shm_) shm_->abort();
+      if (cshm_) cshm_->abort();
+    });
+    else xw_.stop();
     for (StepSlot& sp : par_) sp.b_wait = 0;
   }
 
@@ -2336,23 +2234,48 @@ class Engine {
     return moved;
   }
 
-  // ---- cold store (third body tier), between steps; the host moves the bytes
+  // ---- cold store (third body tier); the host moves the bytes.  Four operations, each either
+  // between steps (cold_*: pipeline drained, on s_comp_) or beside them (side_cold_*, below)
+  enum : int { SIDE_NONE = 0, SIDE_PICK, SIDE_COMMIT, SIDE_SCAN, SIDE_IN, SIDE_LIVE };
+  // the kernel of one of them on stream s, with the memsets it needs; commit / in: op.n
+  // records are in cold_recs_ already
+  void launch_cold(const SideOp& op, hipStream_t s) {
+    const HostIO& io = par_[0].io;
+    switch (op.kind) {
+      case SIDE_PICK:
+        HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s));
+        HIPCHECK(hipMemsetAsync(cold_bytes_, 0, 8, s));
+        hipLaunchKernelGGL(k_cold_pick, dim3(d_.q_max), dim3(256), 0, s, io, op.a, op.b, op.c, cold_recs_, op.max_n,
+                           cold_cnt_, cold_bytes_, op.max_bytes);
+        break;
+      case SIDE_SCAN:
+        HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s));
+        HIPCHECK(hipMemsetAsync(cold_end_, 0, 8ull * d_.q_max, s));
+        hipLaunchKernelGGL(k_cold_scan, dim3(d_.q_max), dim3(64), 0, s, io, op.a, cold_recs_, op.max_n, cold_cnt_,
+                           cold_end_);
+        break;
+      case SIDE_COMMIT:
+        if (op.n) hipLaunchKernelGGL(k_cold_commit, blocks(op.n, 256), dim3(256), 0, s, io, cold_recs_, op.n);
+        break;
+      case SIDE_IN: {
+        const u64 g = op.n > d_.q_max ? op.n : d_.q_max;
+        hipLaunchKernelGGL(k_cold_in, blocks(g, 256), dim3(256), 0, s, io, cold_recs_, op.n, cold_end_);
+        break;
+      }
+    }
+  }
   // out: candidate records (ColdRec[], bytes 0 = skip) for the host to write to the store
   // (slots below spill tail + lim)
   py::bytes cold_pick(u32 hot, u64 lim, u32 max_n, u64 max_bytes) {
     if (!d_.spill_bytes) return py::bytes("");
     between_steps("cold_pick");
     if (max_n > COLD_BATCH) max_n = COLD_BATCH;
-    HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s_comp_));
-    HIPCHECK(hipMemsetAsync(cold_bytes_, 0, 8, s_comp_));
-    hipLaunchKernelGGL(k_cold_pick, dim3(d_.q_max), dim3(256), 0, s_comp_, par_[0].io, hot, lim, (u64)0, cold_recs_,
-                       max_n, cold_cnt_, cold_bytes_, max_bytes);
+    launch_cold(SideOp{SIDE_PICK, hot, lim, 0, max_n, max_bytes, 0}, s_comp_);
     return cold_fetch(max_n);
   }
   // ... the host stored them (ColdRec.cold = store offsets): switch the messages over
   void cold_commit(py::buffer recs) {
-    const u32 n = cold_upload(recs);
-    if (n) hipLaunchKernelGGL(k_cold_commit, blocks(n, 256), dim3(256), 0, s_comp_, par_[0].io, cold_recs_, n);
+    launch_cold(SideOp{SIDE_COMMIT, 0, 0, 0, 0, 0, cold_upload(recs)}, s_comp_);
     HIPCHECK(hipStreamSynchronize(s_comp_));
   }
   // in: the cold entries near the heads of the held queues, each with a spill-ring slot
@@ -2360,33 +2283,25 @@ class Engine {
     if (!d_.spill_bytes) return py::bytes("");
     between_steps("cold_scan");
     if (max_n > COLD_BATCH) max_n = COLD_BATCH;
-    HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s_comp_));
-    HIPCHECK(hipMemsetAsync(cold_end_, 0, 8ull * d_.q_max, s_comp_));
-    hipLaunchKernelGGL(k_cold_scan, dim3(d_.q_max), dim3(64), 0, s_comp_, par_[0].io, window, cold_recs_, max_n, cold_cnt_,
-                       cold_end_);
+    launch_cold(SideOp{SIDE_SCAN, window, 0, 0, max_n, 0, 0}, s_comp_);
     return cold_fetch(max_n);
   }
   // ... the host read their bodies into those slots: back to SPILL_BIT, q_cold_lim moved on
   void cold_in(py::buffer recs) {
-    const u32 n = cold_upload(recs);
-    const u64 g = n > d_.q_max ? n : d_.q_max;
-    hipLaunchKernelGGL(k_cold_in, blocks(g, 256), dim3(256), 0, s_comp_, par_[0].io, cold_recs_, n, cold_end_);
+    launch_cold(SideOp{SIDE_IN, 0, 0, 0, 0, 0, cold_upload(recs)}, s_comp_);
     HIPCHECK(hipStreamSynchronize(s_comp_));
   }
   // ---- the same four operations beside the steps (no pipeline drain, single GPU): the
   // cold thread posts one (side_*), the next launch() runs it on the compute stream between
   // two steps, side_wait() hands back its records; the steps keep flowing while the host
-  // moves bodies between the ring and the store.  A pick is picked up again by the commit
-  // only where its entry is still queued (k_cold_commit); k_cold_scan's ring slots count as
-  // live until k_cold_in.  SIDE_LIVE copies cold_live (store segment GC).
-  enum : int { SIDE_NONE = 0, SIDE_PICK, SIDE_COMMIT, SIDE_SCAN, SIDE_IN, SIDE_LIVE };
+  // moves bodies between the ring and the store (the mailbox: side_box.h).  A pick is picked
+  // up again by the commit only where its entry is still queued (k_cold_commit); k_cold_scan's
+  // ring slots count as live until k_cold_in.  SIDE_LIVE copies cold_live (store segment GC).
   void side_post(int kind, u32 a, u64 b, u64 c, u32 max_n, u64 max_bytes, const ColdRec* recs, u32 n) {
     if (d_.world != 1) throw std::runtime_error("side operations: single-GPU engines only");
     if (!side_h_) throw std::runtime_error("side operations: no spill ring");
-    std::lock_guard<std::mutex> g(side_mu_);
-    if (side_.kind) throw std::runtime_error("side operation pending (side_wait first)");
-    if (n) memcpy((u8*)side_h_ + 64, recs, sizeof(ColdRec) * n);
-    side_ = Side{kind, a, b, c, max_n > COLD_BATCH ? COLD_BATCH : max_n, max_bytes, n, false};
+    side_.post(SideOp{kind, a, b, c, max_n > COLD_BATCH ? COLD_BATCH : max_n, max_bytes, n},
+               [&] { if (n) memcpy((u8*)side_h_ + 64, recs, sizeof(ColdRec) * n); });
   }
   void side_cold_pick(u32 hot, u64 lim_rel, u64 min_used, u32 max_n, u64 max_bytes) {
     side_post(SIDE_PICK, hot, lim_rel, min_used, max_n, max_bytes, nullptr, 0);
@@ -2397,51 +2312,26 @@ class Engine {
   void side_cold_live() { side_post(SIDE_LIVE, 0, 0, 0, 0, 0, nullptr, 0); }
   void side_recs(int kind, py::buffer recs) {
     py::buffer_info bi = recs.request();
-    const size_t nb = (size_t)bi.size * bi.itemsize;
-    if (nb % sizeof(ColdRec) || nb / sizeof(ColdRec) > COLD_BATCH) throw std::runtime_error("cold: bad ColdRec batch");
-    side_post(kind, 0, 0, 0, 0, 0, (const ColdRec*)bi.ptr, (u32)(nb / sizeof(ColdRec)));
+    side_post(kind, 0, 0, 0, 0, 0, (const ColdRec*)bi.ptr, cold_batch(bi));
   }
-  bool side_pending() {
-    std::lock_guard<std::mutex> g(side_mu_);
-    return side_.kind != SIDE_NONE;
-  }
-  bool side_queued() {
-    std::lock_guard<std::mutex> g(side_mu_);
-    return side_.kind && !side_.launched;
-  }
+  bool side_pending() { return side_.pending(); }
   // launch(): the posted operation on stream s, ahead of the step's kernels
   void run_side(hipStream_t s) {
-    std::lock_guard<std::mutex> g(side_mu_);
-    if (!side_.kind || side_.launched) return;
+    const std::optional<SideOp> op = side_.begin_launch();
+    if (!op) return;
     ColdRec* hrecs = (ColdRec*)((u8*)side_h_ + 64);
     ColdRec* drecs = (ColdRec*)((u8*)side_d_ + 64);
-    switch (side_.kind) {
+    switch (op->kind) {
       case SIDE_PICK:
       case SIDE_SCAN:
-        HIPCHECK(hipMemsetAsync(cold_cnt_, 0, 16, s));
-        if (side_.kind == SIDE_PICK) {
-          HIPCHECK(hipMemsetAsync(cold_bytes_, 0, 8, s));
-          hipLaunchKernelGGL(k_cold_pick, dim3(d_.q_max), dim3(256), 0, s, par_[0].io, side_.a, side_.b, side_.c,
-                             cold_recs_, side_.max_n, cold_cnt_, cold_bytes_, side_.max_bytes);
-        } else {
-          HIPCHECK(hipMemsetAsync(cold_end_, 0, 8ull * d_.q_max, s));
-          hipLaunchKernelGGL(k_cold_scan, dim3(d_.q_max), dim3(64), 0, s, par_[0].io, side_.a, cold_recs_, side_.max_n,
-                             cold_cnt_, cold_end_);
-        }
+        launch_cold(*op, s);
         hipLaunchKernelGGL(k_side_out, dim3(64), dim3(256), 0, s, (const ColdRec*)cold_recs_, (const u32*)cold_cnt_,
-                           side_.max_n, (u32*)drecs, (u32*)side_d_);
+                           op->max_n, (u32*)drecs, (u32*)side_d_);
         break;
       case SIDE_COMMIT:
       case SIDE_IN:
-        if (side_.n)
-          HIPCHECK(hipMemcpyAsync(cold_recs_, hrecs, sizeof(ColdRec) * side_.n, hipMemcpyHostToDevice, s));
-        if (side_.kind == SIDE_COMMIT) {
-          if (side_.n)
-            hipLaunchKernelGGL(k_cold_commit, blocks(side_.n, 256), dim3(256), 0, s, par_[0].io, cold_recs_, side_.n);
-        } else {
-          const u64 g2 = side_.n > d_.q_max ? side_.n : d_.q_max;
-          hipLaunchKernelGGL(k_cold_in, blocks(g2, 256), dim3(256), 0, s, par_[0].io, cold_recs_, side_.n, cold_end_);
-        }
+        if (op->n) HIPCHECK(hipMemcpyAsync(cold_recs_, hrecs, sizeof(ColdRec) * op->n, hipMemcpyHostToDevice, s));
+        launch_cold(*op, s);
         break;
       case SIDE_LIVE:
         HIPCHECK(hipMemcpyAsync(side_live_h_, d_.cold_live, 8ull * COLD_SEGS, hipMemcpyDeviceToHost, s));
@@ -2449,8 +2339,7 @@ class Engine {
     }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(ev_side_, s));
-    side_.launched = true;
-    side_cv_.notify_all();
+    side_.launched();
   }
   // the posted operation's result once it ran: ColdRec[] (pick / scan), cold_live bytes
   // (live), b"" (commit / in); None while it has not finished within timeout_s
@@ -2460,24 +2349,18 @@ class Engine {
     bool done = false;
     {
       py::gil_scoped_release nogil;   // (no Python objects in here)
-      std::unique_lock<std::mutex> g(side_mu_);
-      kind = side_.kind;
       const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds((i64)(timeout_s * 1e6));
-      if (kind && side_cv_.wait_until(g, until, [&] { return side_.launched; })) {
-        g.unlock();
-        while (true) {
-          err = hipEventQuery(ev_side_);
-          if (err == hipSuccess) { done = true; break; }
-          if (err != hipErrorNotReady || std::chrono::steady_clock::now() > until) break;
-          std::this_thread::sleep_for(std::chrono::microseconds(50));
-        }
+      kind = side_.wait_launched(until);
+      while (kind) {
+        err = hipEventQuery(ev_side_);
+        if (err == hipSuccess) { done = true; break; }
+        if (err != hipErrorNotReady || std::chrono::steady_clock::now() > until) break;
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
       }
     }
-    if (!kind) throw std::runtime_error("side_wait: nothing posted");
     if (err != hipSuccess && err != hipErrorNotReady) HIPCHECK(err);
     if (!done) return py::none();
-    std::lock_guard<std::mutex> g(side_mu_);
-    side_.kind = SIDE_NONE;
+    side_.clear();
     if (kind == SIDE_PICK || kind == SIDE_SCAN) {
       const u32 n = *(volatile u32*)side_h_;
       return py::bytes((const char*)side_h_ + 64, sizeof(ColdRec) * (size_t)n);
@@ -2502,12 +2385,16 @@ class Engine {
     if (n) HIPCHECK(hipMemcpy(&out[0], cold_recs_, out.size(), hipMemcpyDeviceToHost));
     return py::bytes(out);
   }
-  u32 cold_upload(py::buffer recs) {
-    py::buffer_info bi = recs.request();
+  // a ColdRec[] batch from Python: its record count
+  static u32 cold_batch(const py::buffer_info& bi) {
     const size_t nb = (size_t)bi.size * bi.itemsize;
     if (nb % sizeof(ColdRec) || nb / sizeof(ColdRec) > COLD_BATCH) throw std::runtime_error("cold: bad ColdRec batch");
-    const u32 n = (u32)(nb / sizeof(ColdRec));
-    if (n) HIPCHECK(hipMemcpy(cold_recs_, bi.ptr, nb, hipMemcpyHostToDevice));
+    return (u32)(nb / sizeof(ColdRec));
+  }
+  u32 cold_upload(py::buffer recs) {
+    py::buffer_info bi = recs.request();
+    const u32 n = cold_batch(bi);
+    if (n) HIPCHECK(hipMemcpy(cold_recs_, bi.ptr, sizeof(ColdRec) * (size_t)n, hipMemcpyHostToDevice));
     return n;
   }
 

@@ -1,6 +1,7 @@
 """Host-only checks of the engine's sources: the deferred control-write stager under the
-address and undefined-behaviour sanitizers (a stand-alone program, never loaded into Python),
-and the extension's rebuild list against what engine.hip really includes."""
+address and undefined-behaviour sanitizers, the SDMA copy plan, the exchange worker and the
+side-operation mailbox under those and the thread sanitizer (stand-alone programs, never
+loaded into Python), and the extension's rebuild list against what engine.hip really includes."""
 
 import os
 import re
@@ -24,6 +25,40 @@ def test_delta_stage_under_sanitizers(tmp_path):
                     "-static-libasan", "-static-libubsan", f"-I{KERNELS}",
                     os.path.join(ROOT, "tests", "native", "delta_stage_test.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip() == "ok" and not r.stderr.strip(), r.stdout + r.stderr
+
+
+ENGINE_HOST_TEST = os.path.join(ROOT, "tests", "native", "engine_host_test.cpp")
+
+
+def test_engine_host_logic_under_asan_ubsan(tmp_path):
+    """The SDMA copy plan, the exchange worker and the side-operation mailbox (sdma_plan.h,
+    xchg_worker.h, side_box.h) as a stand-alone program under ASan + UBSan."""
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.fail("g++ is needed to build tests/native/engine_host_test.cpp")
+    exe = str(tmp_path / "engine_host_test")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-static-libasan", "-static-libubsan", "-pthread", f"-I{KERNELS}", ENGINE_HOST_TEST, "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip() == "ok" and not r.stderr.strip(), r.stdout + r.stderr
+
+
+def test_engine_host_logic_under_tsan(tmp_path):
+    """The same program under ThreadSanitizer, built with the ROCm LLVM clang++ as
+    scripts/host_sanitize.sh does: gcc 11's libtsan does not intercept the timed
+    condition-variable wait the side box uses and reports a false double lock there."""
+    cxx = "/opt/rocm/lib/llvm/bin/clang++"
+    if not os.path.exists(cxx):
+        pytest.fail(cxx + " is needed to build tests/native/engine_host_test.cpp with -fsanitize=thread")
+    exe = str(tmp_path / "engine_host_tsan")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread", f"-I{KERNELS}", ENGINE_HOST_TEST,
+                    "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.strip() == "ok" and not r.stderr.strip(), r.stdout + r.stderr
 
