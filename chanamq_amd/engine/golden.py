@@ -805,7 +805,7 @@ class GoldenDataPlane(ControlState):
 
     def _expiration(self, props, now_ms):
         e = self._prop_fields(props).get("expiration")
-        if e and e.isdigit() and len(e) <= 18:
+        if e and e.isascii() and e.isdigit() and len(e) <= 18:   # ASCII digits only, as k_decode reads them
             return now_ms + int(e)
         return 0
 

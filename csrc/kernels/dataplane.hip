@@ -450,13 +450,15 @@ __global__ __launch_bounds__(256) void k_decode(DS d) {
     u32 fl = 0;   // the first property-flags word (continuation words are skipped)
     u32 nfl = 0;
     u32 q = ho;
+    bool fend = false;   // the flags chain ended on a word without the continuation bit
     while (q + 2 <= hend) {
       u32 fw = (pbyte(q) << 8) | pbyte(q + 1);
       q += 2;
       if (nfl == 0) fl = fw;
       ++nfl;
-      if (!(fw & 1)) break;
+      if (!(fw & 1)) { fend = true; break; }
     }
+    if (!fend) fl = 0;   // cut short inside the flags: no properties (as below)
     bool pok = true;
     // field order: 15 ctype ss, 14 cenc ss, 13 headers tbl, 12 dmode oct, 11 prio oct,
     // 10 corr ss, 9 replyto ss, 8 expiration ss, 7 msgid ss, 6 timestamp u64, 5 type,
@@ -508,6 +510,9 @@ __global__ __launch_bounds__(256) void k_decode(DS d) {
           pok = q <= hend;
       }
     }
+    // a list cut short inside a field has no properties at all (the golden model's reading:
+    // the reference's decoder throws on one), whatever was read ahead of the cut
+    if (!pok) { pb.flags &= ~(MF_PERSIST | MF_HAS_TS); pb.expire_ms = 0; pb.ts_ms = 0; }
     pb.nwords = pb.rk_len <= 32 ? build_keyvec_win(d, rkw, pb.rk_len, pi) : build_keyvec(d, w + pb.rk_off, pb.rk_len, pi);
     // egress by reference: a body that is one run of this step's new ingress bytes (not in
     // the connection's carry) keeps its host address -- its deliveries can be sent from

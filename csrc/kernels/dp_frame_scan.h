@@ -80,6 +80,8 @@ constexpr u32 FS_AM_MAX = 8192;  // 128 KB segment; 16 KB of LDS
 // stage, other segments CAND_MAX candidates (a 128 KB segment of 1-byte messages)
 constexpr u32 FS_STAGE = 72u << 10;
 constexpr u32 FS_CAND_STAGED = 6144;
+constexpr u32 FS_RUNS = 1024;   // run records of the chain (phase c), kept at the top of wend
+static_assert(CAND_MAX < (1u << 16) && FS_CAND_STAGED > 2 * FS_RUNS, "k_frame_scan candidate limits");
 // candidate arrays: wend + cpos (u32), chain / screen mask (u16), csucc (i16), claim (u8)
 constexpr u32 fs_cand_bytes(u32 cmax, u32 amw) { return cmax * 4 * 2 + (cmax > amw ? cmax : amw) * 2 + cmax * 2 + cmax; }
 constexpr u32 FS_POOL_STAGED = FS_STAGE + fs_cand_bytes(FS_CAND_STAGED, FS_STAGE / 16);
@@ -410,7 +412,30 @@ DEV void frame_scan_seg(const DS& d, const u32 s, const FsHead hd) {
         if (nmc < cmax) { cpos[nmc] = p; wend[nmc] = ~0u; }
         ++nmc;
       }
-      if (nmc > cmax) { sh_over = 1; nmc = cmax; }
+      if (nmc > cmax) {
+        // more accepted candidates than slots: header lookalikes inside bodies, or that many
+        // frames.  A list cut at cmax may end between a frame and its successor, and the chain
+        // with it, however little of the segment was real frames.  The list becomes the frames
+        // themselves, walked from byte 0 (at most cmax steps, each past a checked header);
+        // phases (b) and (c) then find every successor next in line.  over = the walk itself
+        // ran out of slots: whole frames follow the last one listed
+        u32 n = 0;
+        u64 p = 0;
+        bool cut = false;
+        while (p < L) {
+          if (n == cmax) { cut = true; break; }
+          const FInfo f = frame_at(b, (u32)p, L, fmax);
+          const bool ok = p + 7 > L || (f.valid_hdr && (f.complete || p + 8 + f.size > L));
+          if (!ok) break;   // a broken frame: phase (b) finds no successor for the one before it
+          cpos[n] = (u32)p;
+          wend[n] = ~0u;
+          ++n;
+          if (!f.complete) break;
+          p += 8 + (u64)f.size;
+        }
+        sh_over = cut ? 1u : 0u;
+        nmc = n;
+      }
       sh_m = nmc;
     }
     __syncthreads();
@@ -454,7 +479,6 @@ DEV void frame_scan_seg(const DS& d, const u32 s, const FsHead hd) {
   // header that look like a frame running past the segment end), not one per frame --
   // recording runs, which all threads expand into chain[].  A single run starting at 0
   // is the implicit chain (frame f = candidate f)
-  constexpr u32 FS_RUNS = 1024;            // run records at the top of wend
   const u32 FS_FAIL_MAX = cmax - 2 * FS_RUNS;
   __syncthreads();   // csucc / wend of (b) complete
   FS_MARK(9);
@@ -647,7 +671,10 @@ DEV void frame_scan_seg(const DS& d, const u32 s, const FsHead hd) {
     so.status |= (reason == 3) ? SS_FRAME_ERROR : SS_UNEXPECTED;
     so.err_off = consumed;
   }
-  if (over && reason != 0 && kf == nf) so.status |= SS_OVERFLOW;
+  // the list ran out of slots and the scan stopped for want of frames, at the chain's end or
+  // at a command whose frames run past it: the carry holds whole frames the next step must
+  // see without waiting for new bytes (kf == 0: one command of more frames than slots)
+  if (over && ((reason != 0 && kf == nf) || (reason == 1 && kf > 0))) so.status |= SS_OVERFLOW;
   if (reason == 4) so.status |= SS_OVERFLOW;   // the carry is re-presented to the next step
 
   // split mode: the work buffer gets the carry and the frame that runs from it into the new
@@ -770,10 +797,13 @@ DEV void frame_scan_seg(const DS& d, const u32 s, const FsHead hd) {
     }
     const u32 is_pub = is_cmd && c.kind == CK_PUBLISH;
     const u32 is_ack = is_cmd && (c.kind == CK_ACK || c.kind == CK_NACK || c.kind == CK_REJECT);
-    // one scan of three 11-bit counters (<= FS_NT each per chunk): commands | pubs | acks
-    u32 tpk, tf;
-    const u32 rpk = block_scan<FS_NT>(is_cmd | (is_pub << 11) | (is_ack << 22), sc, tpk);
-    u32 fr = block_scan<FS_NT>(nfr, sc, tf);
+    // two scans of packed counters: commands | pubs (11 bits each, <= FS_NT per chunk), and
+    // fragments | acks (16 bits each: a chunk's fragments are frames of the segment, < 2^16
+    // by CAND_MAX; a chunk that is all acks counts FS_NT of them, 11 bits)
+    u32 tpk, tfa;
+    const u32 rpk = block_scan<FS_NT>(is_cmd | (is_pub << 11), sc, tpk);
+    const u32 rfa = block_scan<FS_NT>(nfr | (is_ack << 16), sc, tfa);
+    const u32 fr = rfa & 0xffffu, tf = tfa & 0xffffu;
     const u32 r = rpk & 0x7ffu, tcnt = tpk & 0x7ffu;
     if (one) {   // the segment's only chunk: reserve its commands / fragments now (as above)
       if (tid == 0) {
@@ -821,8 +851,8 @@ DEV void frame_scan_seg(const DS& d, const u32 s, const FsHead hd) {
       c.seg = s;
       c.raw_off = OFF(p);
       // ordinals within the segment: k_decode numbers publishes / acks segment-major
-      c.pad[1] = npub_run + ((rpk >> 11) & 0x7ffu);
-      c.pad[2] = nack_run + (rpk >> 22);
+      c.pad[1] = npub_run + (rpk >> 11);
+      c.pad[2] = nack_run + (rfa >> 16);
       u32 endp = p + 8 + fi.size;
       if (cls == 60 && mid == 40) {
         c.h_off = OFF(hp) + 7;
@@ -875,8 +905,8 @@ DEV void frame_scan_seg(const DS& d, const u32 s, const FsHead hd) {
     }
     run += tcnt;
     frun += tf;
-    npub_run += (tpk >> 11) & 0x7ffu;
-    nack_run += tpk >> 22;
+    npub_run += tpk >> 11;
+    nack_run += tfa >> 16;
   }
   if (tid == 0 && kf > 0) d.conn_last_rx[conn] = now;
   if (reason == 0) so.status |= SS_CTRL;

@@ -2783,6 +2783,10 @@ PYBIND11_MODULE(_dataplane, m) {
   m.def("device_count", &device_count);
   m.def("create_stream", &create_stream, py::arg("device") = 0);
   m.attr("CAND_MAX") = CAND_MAX;
+  m.attr("FS_CAND_STAGED") = FS_CAND_STAGED;   // the frame scan's limits (dp_frame_scan.h)
+  m.attr("FS_STAGE") = FS_STAGE;
+  m.attr("FS_AM_MAX") = FS_AM_MAX;
+  m.attr("FS_RUNS") = FS_RUNS;
   m.attr("TOPIC_K") = TOPIC_K;
   m.attr("TOPIC_WORDS") = TOPIC_WORDS;
   m.attr("LAT_BINS") = LAT_BINS;

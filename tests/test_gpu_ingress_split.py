@@ -10,8 +10,8 @@ engine makes."""
 
 import pytest
 
-from chanamq_amd.engine.traffic import publish_command
 from dp_scenarios import SCENARIOS, run
+from ingress_scenarios import exact_stream, frames
 
 pytestmark = pytest.mark.gpu
 
@@ -79,36 +79,6 @@ def test_scenarios_default_split(gpu, name):
     assert st["split"] == sum(1 for n in lens if n and splits(n)), (st, lens)
     assert st["unsplit"] == sum(1 for n in lens if n and not splits(n)), (st, lens)
     assert st["runtime"] == 0, st
-
-
-def exact_stream(n):
-    """Publishes of one connection, exactly n bytes of whole commands."""
-    one = lambda size, i: publish_command(1, "", "sq", bytes((i * 7 + j) & 0xff for j in range(size)),
-                                          {"delivery_mode": 1})
-    ovh = len(one(1, 0)) - 1
-    out, total, i = [], 0, 0
-    while n - total > 2 * (ovh + 1000):
-        out.append(one(1000, i))
-        total += len(out[-1])
-        i += 1
-    rest = n - total - ovh
-    if rest > 1200:   # (two commands: neither body empty)
-        out.append(one(rest // 2 - ovh, i))
-        total += len(out[-1])
-        rest = n - total - ovh
-    assert rest >= 1
-    out.append(one(rest, i + 1))
-    data = b"".join(out)
-    assert len(data) == n
-    return data
-
-
-def frames(data):
-    pos = 0
-    while pos < len(data):
-        end = pos + 8 + int.from_bytes(data[pos + 3:pos + 7], "big")
-        yield pos, end
-        pos = end
 
 
 def make_pair(**over):
