@@ -758,6 +758,7 @@ __global__ __launch_bounds__(1024) void k_scan_route(ScanArgs a, u32* tot, u64* 
 // row 0.  The offsets block keeps up to RS_RT tiles' counts in registers: one round of
 // loads, one block scan, one round of stores.
 constexpr u32 RS_RT = 16;
+constexpr u32 RS_RB = 8;   // past RS_RT tiles: tiles per round of the first pass over the histograms
 template <int DB> struct RsNt { static constexpr u32 v = DB > 10 ? 1024u : (DB > 9 ? 512u : 256u); };
 template <int DB>
 DEV void rs_offsets(const u32* hist, u32* hscan, u32 T, u32* lds) {
@@ -792,7 +793,7 @@ DEV void rs_offsets(const u32* hist, u32* hscan, u32 T, u32* lds) {
     return;
   }
   // many tiles: two passes over the histograms, RB tiles at a time
-  constexpr u32 RB = 8;
+  constexpr u32 RB = RS_RB;
   u32 t = 0;
   for (; t + RB <= T; t += RB) {
     u32 h[RB][PER];
@@ -1088,11 +1089,15 @@ DEV void route_emit(const DS& d, RouteAcc<PASS>& a, u32 p, u32 wbase, u32 srank,
   u32 pos = a.nq + (u32)__popcll(lm & lanemask_lt());
   if (local) {
     if (PASS) {
-      if (wbase + pos >= d.pair_max) return;   // pair table full: store_one trims refcnt
-      d.pair_k[0][wbase + pos] = (q << d.rank_bits) | srank;
-      d.pair_v[0][wbase + pos] = p;
-    } else if (pos < 8) {
-      d.pub_qc[(u64)p * 8 + pos] = q;
+      // every lane counts (a.nq stays uniform over the chunks); only a lane whose pair lies
+      // within the pair table stores it, so a full table keeps the pairs of the lowest queues
+      // (store_one trims refcnt to those)
+      if (wbase + pos < d.pair_max) {
+        d.pair_k[0][wbase + pos] = (q << d.rank_bits) | srank;
+        d.pair_v[0][wbase + pos] = p;
+      }
+    } else if (pos < PUB_QC) {
+      d.pub_qc[(u64)p * PUB_QC + pos] = q;
     }
   }
   a.nq += (u32)__popcll(lm);
@@ -1154,7 +1159,7 @@ DEV void hop_finish(const DS& d, RouteAcc<0>& a, const HopWalk& h, const Pub& pb
   // more than 8 local queues: a run of hop_q for pass 1.  Only a publish that is enqueued
   // reserves (an immediate publish without a consumer is returned with 313: no pairs), so
   // the reservations never add up to more than the step's pairs
-  if (a.nq <= 8 || ((pb.flags & (MF_IMMEDIATE | MF_IMPORTED)) == MF_IMMEDIATE && !a.has_cons)) return;
+  if (a.nq <= PUB_QC || ((pb.flags & (MF_IMMEDIATE | MF_IMPORTED)) == MF_IMMEDIATE && !a.has_cons)) return;
   u32 off = lane == 0 ? atomicAdd(&d.tot[TS_HOP_N], a.nq) : 0u;
   off = (u32)__shfl((int)off, 0);
   if (off + a.nq > d.pair_max) {
@@ -1181,7 +1186,7 @@ DEV void hop_finish(const DS& d, RouteAcc<0>& a, const HopWalk& h, const Pub& pb
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  if (lane == 0) d.pub_qc[(u64)p * 8] = XT_EDGE | off;
+  if (lane == 0) d.pub_qc[(u64)p * PUB_QC] = XT_EDGE | off;
 }
 
 template <int PASS>
@@ -1203,9 +1208,9 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
     const u32 fit = d.pair_max - wbase < nq0 ? d.pair_max - wbase : nq0;
     // routing result cached by pass 0: up to 8 queues in pub_qc; the longer list of a walk
     // (exchange-to-exchange edges) in a run of hop_q, its offset under XT_EDGE in pub_qc[0]
-    const u32 q0 = d.pub_qc[(u64)p * 8];
-    if (nq0 <= 8 || (q0 & XT_EDGE)) {
-      const u32* run = nq0 <= 8 ? d.pub_qc + (u64)p * 8 : d.hop_q + (q0 & ~XT_EDGE);
+    const u32 q0 = d.pub_qc[(u64)p * PUB_QC];
+    if (nq0 <= PUB_QC || (q0 & XT_EDGE)) {
+      const u32* run = nq0 <= PUB_QC ? d.pub_qc + (u64)p * PUB_QC : d.hop_q + (q0 & ~XT_EDGE);
       for (u32 k = lane; k < fit; k += 64) {
         d.pair_k[0][wbase + k] = (run[k] << d.rank_bits) | srank;
         d.pair_v[0][wbase + k] = p;
@@ -1821,7 +1826,7 @@ DEV void import_one(const DS& d, u32 i, const u32* xr) {
     const u32 slot = nq ? align16(align16(pb.ex_len + pb.rk_len + pb.props_len) + pb.body_size) : 0u;
     pb.nq = nq;
     pb.slot_bytes = slot;
-    d.pub_qc[(u64)pi * 8] = q;
+    d.pub_qc[(u64)pi * PUB_QC] = q;
     d.pub_nq[pi] = nq;
     d.pub_slot[pi] = slot;
     d.pub_routed[pi] = nq;

@@ -11,6 +11,8 @@
 #define SORT_TILE 1024        // radix-sort tile (256 threads x 4): more tiles, more blocks in flight
 #define TOPIC_K 256           // topic key vector: 8 words x 32 hash bits (int8 +-1)
 #define TOPIC_WORDS 8
+#define PUB_QC 8              // queues of a publish that route pass 0 caches for pass 1 (a pub_qc row)
+#define SORT_ONEPASS_BITS 11  // widest pair key (queue | rank bits) sorted in one pass, enqueue fused
 #define LAT_BINS 32
 #define WORLD_MAX 16          // ranks of one sharded broker (one node: 8 GPUs)
 #define INGRESS_SLOTS 3       // rotating ingress payload buffers (StepIn.ingress)
@@ -157,7 +159,7 @@ struct DS {
   u16* pub_kwoff;           // [pub_max][TOPIC_WORDS] routing-key words: offset << 8 | length
   u16* pub_match;           // [pub_max][tb_pad/16]
   u32* pub_nq;
-  u32* pub_qc;              // [pub_max][8] routed queues cached by route pass 0 ([0] = XT_EDGE | offset
+  u32* pub_qc;              // [pub_max][PUB_QC] routed queues cached by route pass 0 ([0] = XT_EDGE | offset
                             // of the publish's run in hop_q: a walk that reached more than 8)
   u32* pub_slot;
   u32* pub_routed;

@@ -364,7 +364,7 @@ class Engine {
     d_.pub_kwoff = (u16*)dev("pub_kwoff", 2ull * TOPIC_WORDS * d_.pub_cap + 64);
     d_.pub_match = (u16*)dev("pub_match", 2ull * d_.pub_cap * (d_.tb_pad / 16) + 64);
     d_.pub_nq = (u32*)dev("pub_nq", 4ull * d_.pub_cap);
-    d_.pub_qc = (u32*)dev("pub_qc", 32ull * d_.pub_cap);
+    d_.pub_qc = (u32*)dev("pub_qc", 4ull * PUB_QC * d_.pub_cap);
     d_.pub_slot = (u32*)dev("pub_slot", 4ull * d_.pub_cap);
     d_.pub_routed = (u32*)dev("pub_routed", 4ull * d_.pub_cap);
     d_.pub_pair_off = (u32*)dev("pub_pair_off", 4ull * d_.pub_cap);
@@ -2585,7 +2585,7 @@ class Engine {
   // returns index (0/1) of the buffer holding the sorted output
   u32 radix_sort(hipStream_t s, const DS& d, u32** keys, u32** vals, const u32* n, u32 nmax, u32 bits) {
     const u32 ntiles = ceil_div(nmax, SORT_TILE);
-    const u32 digit = bits > 8 && bits <= 11 ? bits : 8;   // one 9..11-bit pass instead of two 8-bit ones
+    const u32 digit = bits > 8 && bits <= SORT_ONEPASS_BITS ? bits : 8;   // one 9..11-bit pass instead of two 8-bit ones
     u32 src = 0;
     for (u32 shift = 0; shift < bits; shift += digit) {
       with_key_bits(digit, [&](auto b) {
@@ -2664,7 +2664,7 @@ class Engine {
     Range rg("chanamq.K7-K11.tail");
     u32 nch = d.c_max * d.chpc;
     const u32 pbits = d.q_bits + d.rank_bits;
-    if (pbits <= 11) {
+    if (pbits <= SORT_ONEPASS_BITS) {
       // single-pass sort with the ring plan folded into the histogram's last block and the
       // enqueue into the scatter (k_rs_hist_plan / k_rs_scatter_enq): two launches
       const u32 nt = ceil_div(d.pair_max, SORT_TILE);
@@ -2789,6 +2789,11 @@ PYBIND11_MODULE(_dataplane, m) {
   m.attr("FS_RUNS") = FS_RUNS;
   m.attr("TOPIC_K") = TOPIC_K;
   m.attr("TOPIC_WORDS") = TOPIC_WORDS;
+  m.attr("SORT_TILE") = SORT_TILE;   // the sort / enqueue limits (dataplane.hip)
+  m.attr("RS_RT") = RS_RT;
+  m.attr("RS_RB") = RS_RB;
+  m.attr("PUB_QC") = PUB_QC;
+  m.attr("SORT_ONEPASS_BITS") = SORT_ONEPASS_BITS;
   m.attr("LAT_BINS") = LAT_BINS;
   py::class_<Engine>(m, "Engine")
       .def(py::init<py::dict>())
