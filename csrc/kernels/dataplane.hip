@@ -3231,7 +3231,9 @@ DEV void render_deliv(const DS& d, u32 i, u32 lane) {
             d.dv_off[f];
   if (gt && lane == 0)   // (a referenced body goes after its body frame's 7-byte header)
     gt[i] = ref ? EgressRef{href, (u32)(off + dv.size - 1u), m.body_len} : EgressRef{0ull, (u32)(off + dv.size), 0u};
-  if (off + dv.size > d.egress_cap) return;  // never: dequeue reserves an egress byte budget
+  // never: dequeue reserves an egress byte budget.  (Against the buffer, not egress_cap: that
+  // bounds the step's deliveries, and off also counts the returns and confirms in front)
+  if (off + dv.size > d.egress_alloc) return;
   u8* o = (u8*)d.in->egress + off;
   u32 chno = d.ch_num[ch];
   const bool get = dv.flags & DV_GET;   // Basic.GetOk (60/71): no consumer tag, message-count last

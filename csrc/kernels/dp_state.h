@@ -92,6 +92,7 @@ struct DS {
   u32 ucap_mask, deliver_cap, chmap_size, xhash_mask, dhash_mask, tb_max, tb_pad, req_max;
   u32 q_bits, ch_bits, hash_wildcard, frame_max_global;
   u64 log_bytes, log_block, n_log_blocks, work_cap, ingress_cap, egress_cap, ctrl_cap, ring_pool;
+  u64 egress_alloc;         // bytes of one egress buffer: egress_cap for deliveries + returns, confirms, gather table
 
   // ---------------- step io
   StepIn* in;               // device copy of the step's StepIn (k_stage writes it)

@@ -294,12 +294,20 @@ class Engine {
     wait_ms_ = (u32)get("wait_timeout_ms", 10000);
     sdma_split_ = cfg.contains("sdma_split") ? std::max(1, std::min(2, cfg["sdma_split"].cast<int>())) : 1;
 
+    // a step's egress: deliveries and Basic.GetEmpty frames (k_dequeue's byte budget:
+    // egress_cap), returns (each its publish's bytes from the work buffer with the reply
+    // text, at most 72 bytes, in place of the ticket and flags: work_cap + 72 per publish),
+    // one 21-byte confirm per channel, then the gather table of egress by reference (16-byte
+    // aligned, one EgressRef per delivery)
+    egress_alloc_ = d_.egress_cap + d_.work_cap + 72ull * d_.pub_max + (u64)nch * 21 + 4096 + 16ull * d_.deliv_max;
+    d_.egress_alloc = egress_alloc_;
+    if (egress_alloc_ + 8192 > (4ull << 30))
+      throw std::runtime_error("egress buffer must stay below 4 GiB (u32 offsets): lower egress_cap / ingress_cap");
+
     // ---- allocations
     auto dev = [&](const char* name, size_t bytes) { return alloc(name, bytes, false); };
     auto hst = [&](const char* name, size_t bytes) { return alloc(name, bytes, true); };
     d_.ctr = (Counters*)dev("ctr", sizeof(Counters));
-    // (+ the gather table of egress by reference: one EgressRef per delivery)
-    egress_alloc_ = d_.egress_cap + d_.work_cap + (u64)nch * 21 + 4096 + 16ull * d_.deliv_max;
     // the two parities' work buffers and the ingress slots in one allocation, the slots
     // last: a u32 offset from either work buffer reaches them, so a segment without a
     // carry is scanned and read where its H2D put it (k_frame_scan in place: no work copy)
@@ -922,6 +930,7 @@ class Engine {
     o["ingress_cap"] = d_.ingress_cap; o["egress_cap"] = d_.egress_cap; o["ring_pool"] = d_.ring_pool;
     o["work_cap"] = d_.work_cap; o["total_bytes"] = total_bytes_; o["req_max"] = d_.req_max;
     o["carry_budget"] = carry_budget_;
+    o["egress_alloc"] = egress_alloc_; o["pub_max"] = d_.pub_max;
     o["exchange_lag"] = lag_ ? 1 : 0;
     o["native_xchg"] = native_x_ ? 1 : 0;
     o["rccl_standin"] = (rccl_ && cmqx::RcclLib::get().standin) ? 1 : 0;   // (tests/rccl_standin: not RCCL)
@@ -1513,6 +1522,14 @@ class Engine {
     o["engine"] = h2d_hsa_ && ing_engine_ ? __builtin_ctz((u32)ing_engine_) : -1;
     o["engine2"] = h2d_hsa_ && ing_engine2_ ? __builtin_ctz((u32)ing_engine2_) : -1;
     return o;
+  }
+
+  // delivery runs of the finished step of parity p (TS_NRUNS: k_dequeue's count, what
+  // k_dv_write chooses its path by); a device read, for tests
+  u32 step_runs(int p) {
+    u32 v = 0;
+    io_copy(&v, par(p).io.tot + TS_NRUNS, sizeof(v), hipMemcpyDeviceToHost);
+    return v;
   }
 
   py::dict counters(int p) {
@@ -2795,6 +2812,10 @@ PYBIND11_MODULE(_dataplane, m) {
   m.attr("PUB_QC") = PUB_QC;
   m.attr("SORT_ONEPASS_BITS") = SORT_ONEPASS_BITS;
   m.attr("LAT_BINS") = LAT_BINS;
+  m.attr("DVW_LDS") = DVW_LDS;   // the delivery layout / render limits (dataplane.hip)
+  m.attr("CONN_LAYOUT_MAX") = CONN_LAYOUT_MAX;
+  m.attr("RC_RET_BLOCKS") = RC_RET_BLOCKS;
+  m.attr("RD_G") = RD_G;
   py::class_<Engine>(m, "Engine")
       .def(py::init<py::dict>())
       .def("info", &Engine::info)
@@ -2808,6 +2829,7 @@ PYBIND11_MODULE(_dataplane, m) {
       .def("launch", &Engine::launch)
       .def("prefetch", &Engine::prefetch, py::arg("payload_ptr"), py::arg("payload_len"))
       .def("persist_slot", &Engine::persist_slot)
+      .def("step_runs", &Engine::step_runs)
       .def("stage_unpause", &Engine::stage_unpause)
       .def("stage_gets", [](Engine& e, py::buffer b) {
              py::buffer_info bi = b.request();
