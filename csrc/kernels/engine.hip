@@ -954,6 +954,7 @@ class Engine {
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
     o["restore_max"] = restore_max_;
     o["xfer_desc_max"] = d_.xfer_desc_max; o["xfer_bytes"] = d_.xfer_bytes; o["world_max"] = WORLD_MAX;
+    o["pk_tile"] = PK_TILE;   // publishes per k_pack_scan tile
     o["sizeof"] = py::dict(py::arg("StepIn") = sizeof(StepIn), py::arg("SegIn") = sizeof(SegIn),
                            py::arg("SegOut") = sizeof(SegOut), py::arg("Counters") = sizeof(Counters),
                            py::arg("CtrlRec") = sizeof(CtrlRec), py::arg("ConnOut") = sizeof(ConnOut),
@@ -2084,7 +2085,7 @@ class Engine {
       rb += (u64)h[1] + h[3];
       rk += h[4];
     }
-    if (rn > d_.import_max || rb > d_.import_bytes || (rk && (!links_ || rk > (u64)d_.world * d_.lk_cap)))
+    if (rn > d_.import_max || rb > d_.import_bytes || (rk && (!links_ || rk > (u64)(d_.world - 1) * d_.lk_cap)))
       throw std::runtime_error("exchange: received records exceed the import buffers");
     u8* R_d = par_[q].xr_desc;
     u8* R_p = par_[q].xr_pay;
@@ -2420,6 +2421,7 @@ class Engine {
   u32 restore(py::buffer desc, py::buffer pay, i64 now_ms) {
     py::buffer_info di = desc.request(), pi = pay.request();
     u64 db = (u64)di.size * di.itemsize, pb = (u64)pi.size * pi.itemsize;
+    if (db % sizeof(RDesc)) throw std::runtime_error("restore: descriptors are no whole records");
     u32 n = (u32)(db / sizeof(RDesc));
     // native exchange: restores run at a synchronisation point (no import pending) through
     // parity 0's receive buffers
@@ -2427,6 +2429,21 @@ class Engine {
     const u8* rpay = d_.recv_pay ? d_.recv_pay : (native_x_ ? par_[0].io.recv_pay : nullptr);
     if (!rdesc || n > d_.import_max || pb > d_.xfer_bytes)
       throw std::runtime_error("restore batch exceeds the import buffers (restore_max / restore_bytes)");
+    // import_one indexes q_owner with a routed record's tq and ch_pub_fail with a host
+    // publish's channel slot, route_one the exchange tables with exch (below 0: no exchange),
+    // and the payload is read at pay_off, all as given
+    const RDesc* hd = (const RDesc*)di.ptr;
+    for (u32 i = 0; i < n; ++i) {
+      const RDesc& r = hd[i];
+      if ((r.flags & (MF_RESTORE | MF_ONEQ)) && r.tq >= d_.q_max)
+        throw std::runtime_error("restore: record " + std::to_string(i) + " names queue slot " + std::to_string(r.tq));
+      if ((r.flags & MF_HOSTPUB) && (r.pad[0] >= d_.c_max * d_.chpc || r.pad[1] >= d_.c_max))
+        throw std::runtime_error("restore: record " + std::to_string(i) + " names a channel out of range");
+      if (r.exch >= (i32)d_.x_max)
+        throw std::runtime_error("restore: record " + std::to_string(i) + " names exchange slot " + std::to_string(r.exch));
+      if ((u64)r.pay_off + r.ex_len + r.rk_len + r.props_len + r.body_len > pb)
+        throw std::runtime_error("restore: record " + std::to_string(i) + " ends past its payload");
+    }
     between_steps("restore");
     drain_egress();
     if (db) HIPCHECK(hipMemcpy((void*)rdesc, di.ptr, db, hipMemcpyHostToDevice));
@@ -2816,6 +2833,8 @@ PYBIND11_MODULE(_dataplane, m) {
   m.attr("CONN_LAYOUT_MAX") = CONN_LAYOUT_MAX;
   m.attr("RC_RET_BLOCKS") = RC_RET_BLOCKS;
   m.attr("RD_G") = RD_G;
+  m.attr("PK_TILE") = PK_TILE;   // the cross-rank pack's limits (info() has them too)
+  m.attr("WORLD_MAX") = (u32)WORLD_MAX;
   py::class_<Engine>(m, "Engine")
       .def(py::init<py::dict>())
       .def("info", &Engine::info)
