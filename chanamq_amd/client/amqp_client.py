@@ -86,13 +86,13 @@ class Channel:
     def exchange_delete(self, exchange, if_unused=False):
         return self._rpc("exchange.delete", "exchange.delete_ok", exchange=exchange, if_unused=if_unused)
 
-    def exchange_bind(self, destination, source, routing_key=""):
+    def exchange_bind(self, destination, source, routing_key="", arguments=None):
         return self._rpc("exchange.bind", "exchange.bind_ok", destination=destination, source=source,
-                         routing_key=routing_key)
+                         routing_key=routing_key, arguments=arguments or {})
 
-    def exchange_unbind(self, destination, source, routing_key=""):
+    def exchange_unbind(self, destination, source, routing_key="", arguments=None):
         return self._rpc("exchange.unbind", "exchange.unbind_ok", destination=destination, source=source,
-                         routing_key=routing_key)
+                         routing_key=routing_key, arguments=arguments or {})
 
     def queue_declare(self, queue="", passive=False, durable=False, exclusive=False, auto_delete=False,
                       arguments=None):
@@ -103,8 +103,9 @@ class Channel:
         return self._rpc("queue.bind", "queue.bind_ok", queue=queue, exchange=exchange, routing_key=routing_key,
                          arguments=arguments or {})
 
-    def queue_unbind(self, queue, exchange, routing_key=""):
-        return self._rpc("queue.unbind", "queue.unbind_ok", queue=queue, exchange=exchange, routing_key=routing_key)
+    def queue_unbind(self, queue, exchange, routing_key="", arguments=None):
+        return self._rpc("queue.unbind", "queue.unbind_ok", queue=queue, exchange=exchange, routing_key=routing_key,
+                         arguments=arguments or {})
 
     def queue_purge(self, queue):
         return self._rpc("queue.purge", "queue.purge_ok", queue=queue).message_count

@@ -22,7 +22,7 @@ from .layout import (CONN_OUT, CONSUMED_REC, EGRESS_REF, RING_MOVE, CTRL_REC, CT
                      MF_HOSTPUB, MF_PERSIST,
                      MF_ONEQ, MF_REDELIVERED, MF_RESTORE,
                      PERSIST_HDR, RDESC, SEG_IN, SEG_OUT, SS_CTRL, US_ACKED, US_PENDING, US_REQUEUE, USLOT,
-                     chan_hash, direct_key, exch_hash, fnv1a64, topic_pattern_row, topic_word_offsets)
+                     chan_hash, direct_key, exch_hash, fnv1a32, fnv1a64, topic_pattern_row, topic_word_offsets)
 
 ONES64 = np.uint64((1 << 64) - 1)
 
@@ -71,8 +71,13 @@ class StepResult:
 
 class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
-                 world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0, **cfg):
-        """``egress_ref``: egress by reference -- a delivery whose body arrived in the
+                 world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
+                 headers_match=False, **cfg):
+        """``headers_match``: headers exchanges match on their bindings' arguments (the
+        headers branch of route_one; engine cfg hb_max / hp_max bound its tables).  Off: they
+        route as topic.
+
+        ``egress_ref``: egress by reference -- a delivery whose body arrived in the
         ingress payload of the same step (or up to ``egress_ref`` steps earlier) is rendered
         without the body, which the host takes from that payload (``finish`` / ``host_egress``
         splice it back in; the native front end sends it with sendmsg iovecs).  The caller
@@ -146,10 +151,11 @@ class GpuDataPlane(ControlState):
         # bounds of the device's exchange-to-exchange walk (control.py checks them at bind time)
         self.hop_qmax, self.hop_xslots, self.hopx_max = i["hop_qmax"], i["hop_xslots"], i["hopx_max"]
         self.tb_max = i["tb_max"]
+        self.hb_max, self.hp_max, self.hb_pairs, self.kpool_max = i["hb_max"], i["hp_max"], i["hb_pairs"], i["kpool"]
         super().__init__(c_max=i["c_max"], chpc=i["chpc"], q_max=i["q_max"], x_max=i["x_max"],
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
-                         shard_map=shard_map)
+                         shard_map=shard_map, headers_match=headers_match)
 
     # ================================================================== uploads
     # ``defer`` (set by the broker around control work done while steps keep running): table
@@ -215,6 +221,10 @@ class GpuDataPlane(ControlState):
         d_x_off = np.zeros(dh, np.uint32)
         d_x_n = np.zeros(dh, np.uint32)
         tb = []   # (exch, queue, pattern)
+        # headers exchanges matched on arguments (dp_headers.h): rows and their pairs
+        x_h_off = np.zeros(self.x_max, np.uint32)
+        x_h_n = np.zeros(self.x_max, np.uint32)
+        hrows, hpairs = [], []   # (queue | edge, meta, first pair); HP_WORDS words per pair
         for x in sorted(self.exchanges.values(), key=lambda e: e.slot):
             h = exch_hash(self.vhosts[x.vhost], x.name.encode())
             for j in range(xh):
@@ -225,8 +235,22 @@ class GpuDataPlane(ControlState):
                     break
             else:
                 raise ControlError(C.RESOURCE_ERROR, "exchange hash full")
-            x_type[x.slot] = C.EXCHANGE_TYPE_ID[x.type] | (0x100 if x.xbindings else 0)
-            if x.type == "fanout":
+            x_type[x.slot] = C.EXCHANGE_TYPE_ID[x.type] | (0x100 if x.xbindings or x.hxbindings else 0)
+            if self._by_args(x):
+                # XF_HMATCH, and always XF_HOP: its publishes are routed as a walk, edges or none
+                # (the queue list goes through hop_q to pass 1, which then never matches again)
+                x_type[x.slot] |= 0x300
+                x_h_off[x.slot] = len(hrows)
+                # rows sorted by queue slot, the edges (destination under the top bit) after them
+                rows = sorted(set(x.hbindings)) + sorted({(0x80000000 | s, k, a) for s, k, a in x.hxbindings})
+                x_h_n[x.slot] = len(rows)
+                for dst, _, (any_, pairs) in rows:
+                    hrows.append((dst, len(pairs) | (0x100 if any_ else 0), len(hpairs)))
+                    for name, void, cls, val in pairs:
+                        hpairs.append((fnv1a32(name), fnv1a32(val), len(kpool), len(kpool) + len(name), len(val),
+                                       len(name) | ((1 if void else 0) | (2 if cls else 0)) << 24))
+                        kpool += name + val
+            elif x.type == "fanout":
                 qs = sorted({q for q, _ in x.bindings})
                 x_fan_off[x.slot] = len(fan_q)
                 x_fan_n[x.slot] = len(qs)
@@ -276,6 +300,11 @@ class GpuDataPlane(ControlState):
             raise ControlError(C.RESOURCE_ERROR, "too many topic bindings for the GPU table")
         if max(len(fan_x), len(d_x)) > i["hopx_max"]:
             raise ControlError(C.RESOURCE_ERROR, "too many exchange-to-exchange bindings")
+        if len(hrows) > i["hb_max"] or len(hpairs) > i["hp_max"]:
+            raise ControlError(C.RESOURCE_ERROR, "too many headers bindings for the GPU table")
+        h_rows = np.array(hrows, np.uint32).reshape(-1, 3)
+        self.h_used = (len(hrows), len(hpairs))   # (rows, pairs) in use; in info beside their capacities
+        i["hb_used"], i["hp_used"] = self.h_used
         t_queue = np.zeros(tbp, np.uint32)
         t_exch = np.zeros(tbp, np.uint32)
         t_kb_off = np.zeros(tbp, np.uint32)
@@ -291,6 +320,8 @@ class GpuDataPlane(ControlState):
             t_kb_off[n], t_kb_len[n] = len(kpool), len(k)
             kpool += k
             t_mat[n] = row
+        if len(kpool) > i["kpool"]:
+            raise ControlError(C.RESOURCE_ERROR, "key pool full")
         for name, arr in (("x_hkey", x_hkey), ("x_hval", x_hval), ("x_type", x_type),
                           ("x_fan_off", x_fan_off), ("x_fan_n", x_fan_n), ("x_t_off", x_t_off),
                           ("x_t_n", x_t_n), ("x_fanx_off", x_fanx_off), ("x_fanx_n", x_fanx_n),
@@ -299,8 +330,15 @@ class GpuDataPlane(ControlState):
                           ("t_queue", t_queue), ("t_exch", t_exch), ("t_kb_off", t_kb_off),
                           ("t_kb_len", t_kb_len), ("t_flags", t_flags), ("t_expect", t_expect),
                           ("t_mat", t_mat), ("t_woff", t_woff),
-                          ("t_count", np.array([len(tb), 0, 0, 0], np.uint32))):
+                          ("t_count", np.array([len(tb), 0, 0, 0], np.uint32)),
+                          ("x_h_off", x_h_off), ("x_h_n", x_h_n)):
             self._up_diff(name, arr)
+        if hrows:
+            self._up_diff("h_queue", h_rows[:, 0])
+            self._up_diff("h_meta", h_rows[:, 1])
+            self._up_diff("h_pair", h_rows[:, 2])
+        if hpairs:
+            self._up_diff("hp", np.array(hpairs, np.uint32))
         if fan_q:
             self._up_diff("fan_q", np.array(fan_q, np.uint32))
         if d_q:

@@ -475,7 +475,8 @@ class GoldenDataPlane(ControlState):
                 x = self.exch_by_slot.get(exch)
                 if x is None:
                     continue
-                qs = [q for q in self._route(x, rk) if self.queue_by_slot[q].owner == self.rank]
+                # (the owner's re-match, from the record's own property bytes)
+                qs = [q for q in self._route(x, rk, props) if self.queue_by_slot[q].owner == self.rank]
                 if not qs:
                     continue
                 msg = _Msg(ex, rk, props, body, len(qs), self.step_no, flags & MF_PERSIST, mid=self._mid())
@@ -705,7 +706,7 @@ class GoldenDataPlane(ControlState):
             cnt["n_unknown_exchange"] += 1
             out["events"].append((conn, 404, s))
             return
-        qs = self._route(x, rk)
+        qs = self._route(x, rk, props)
         remote = sorted({self.queue_by_slot[q].owner for q in qs} - {self.rank}) if self.world > 1 else []
         ret = 0
         if not qs:
@@ -768,12 +769,14 @@ class GoldenDataPlane(ControlState):
                                           msg.props, msg.body))
             ring.append((msg, False, e))
 
-    def _route(self, x, rk):
-        if x.xbindings:   # exchange-to-exchange edges: the closure, each exchange matched once
-            return self.route_closure(x, rk, self._route_flat)
-        return self._route_flat(x, rk)
+    def _route(self, x, rk, props=b""):
+        if x.xbindings or x.hxbindings:   # exchange-to-exchange edges: the closure, each exchange matched once
+            return self.route_closure(x, rk, self._route_flat, props)
+        return self._route_flat(x, rk, props)
 
-    def _route_flat(self, x, rk):
+    def _route_flat(self, x, rk, props=b""):
+        if self._by_args(x):   # headers-match: by the bindings' arguments (models/matcher.py)
+            return self._match_flat(x, rk, x.hbindings, props)
         if x.type == "direct":
             seen = []
             for q, k in x.bindings:

@@ -177,15 +177,35 @@ class GpuPersistence:
         self.store.force_delete_queue(qid)
         self.store.delete_binds_of_queue(qid)
 
-    def bind(self, vhost, queue, exchange, key):
+    def _bind_row(self, x, q, key):
+        """The arguments of every binding of (x, q, key) the plane holds, as the store row's
+        map; None: no such binding.  (Off, or not a headers exchange: the empty map.)"""
+        from ..models.matcher import args_to_map
+        kb = key.encode() if isinstance(key, str) else bytes(key)
+        if self.plane._by_args(x):
+            mine = [b[2] for b in x.hbindings if b[0] == q.slot and b[1] == kb]
+            return args_to_map(mine) if mine else None
+        return {} if (q.slot, kb) in x.bindings else None
+
+    def bind(self, vhost, queue, exchange, key, arguments=None):
+        """After the plane's bind: the store row of (exchange, queue, key).  A headers
+        exchange matched on arguments may hold several bindings there; the row lists all."""
         x = self.plane.exchanges.get((vhost, exchange))
         q = self.plane.queues.get((vhost, queue))
         if x is not None and q is not None and x.durable and q.durable and exchange and \
                 not exchange.startswith("amq."):
-            self.store.insert_bind(entity_id(vhost, exchange), entity_id(vhost, queue), key, {})
+            row = self._bind_row(x, q, key)
+            self.store.insert_bind(entity_id(vhost, exchange), entity_id(vhost, queue), key, row or {})
 
-    def unbind(self, vhost, queue, exchange, key):
-        self.store.delete_bind(entity_id(vhost, exchange), entity_id(vhost, queue), key)
+    def unbind(self, vhost, queue, exchange, key, arguments=None):
+        """After the plane's unbind: the row goes when its last binding went."""
+        x = self.plane.exchanges.get((vhost, exchange))
+        q = self.plane.queues.get((vhost, queue))
+        row = self._bind_row(x, q, key) if x is not None and q is not None else None
+        if row:
+            self.store.insert_bind(entity_id(vhost, exchange), entity_id(vhost, queue), key, row)
+        else:
+            self.store.delete_bind(entity_id(vhost, exchange), entity_id(vhost, queue), key)
 
     # ------------------------------------------------------------------ failover
     def adopt(self, src, queues, now_ms=None):
@@ -278,7 +298,7 @@ class GpuPersistence:
             p.ensure_vhost(v)
             p.declare_exchange(v, name, tpe, durable=durable, auto_delete=autodel, internal=internal,
                                arguments=args)
-            binds += [(v, _split_eid(qid)[1], name, key) for qid, key, _ in bl]
+            binds += [(v, _split_eid(qid)[1], name, key, dict(a or {})) for qid, key, a in bl]
         items, rewrite = [], []
         for qid in st.queue_ids():
             r = st.select_queue(qid)
@@ -304,9 +324,11 @@ class GpuPersistence:
                 rewrite.append((qid, off, new_off, mid, len(body), red))
                 self.refs[mid] = self.refs.get(mid, 0) + 1
                 new_off += 1
-        for v, q, x, key in binds:
+        from ..models.matcher import args_from_map
+        for v, q, x, key, amap in binds:
             if (v, q) in p.queues:
-                p.bind(v, q, x, key)
+                for cargs in args_from_map(amap):   # (one binding, without arguments, unless headers-match wrote it)
+                    p.bind(v, q, x, key, cargs)
         n = p.restore(items, now_ms) if items else 0
         # new ids strictly above every stored one (snowflake ms field), even if the device
         # clock ran ahead of the wall clock before the restart or the clock went back

@@ -15,6 +15,7 @@ from .comm import Comm
 REPLICATED = {"declare_exchange", "delete_exchange", "declare_queue", "delete_queue", "bind", "unbind",
               "bind_exchange", "unbind_exchange",
               "place_queue", "ensure_vhost", "link_open", "link_close", "link_pull", "link_got", "big_publish"}
+ARG_OPS = {"bind", "unbind", "bind_exchange", "unbind_exchange"}   # (vhost, a, b, key, arguments)
 
 
 class ControlLog:
@@ -34,7 +35,13 @@ class ControlLog:
         if op not in REPLICATED:
             raise ValueError(f"{op} is not a replicated control op")
         seq = len(self.outbox)
-        self.outbox.append([op, list(args), kw])
+        args = list(args)
+        if op in ARG_OPS and len(args) > 4 and args[4] is not None:
+            # binding arguments travel in their canonical form (models/matcher.py): what a
+            # headers exchange matches on, and JSON like the rest of the op
+            from ..models.matcher import args_json
+            args[4] = args_json(args[4])
+        self.outbox.append([op, args, kw])
         if blob is not None:
             self.blobs[seq] = (bytes(blob), sorted({int(r) for r in blob_to}))
         return seq
@@ -109,6 +116,9 @@ class ControlLog:
             return p.set_queue_owner(q.slot, rank)
         if op == "ensure_vhost":
             return p.ensure_vhost(*args)
+        if op in ARG_OPS and len(args) > 4:
+            from ..models.matcher import args_unjson
+            args = list(args[:4]) + [args_unjson(args[4])] + list(args[5:])
         return getattr(p, op)(*args, **kw)
 
 

@@ -219,7 +219,7 @@ class GpuBroker:
                  ingress_bytes=64 << 20, per_conn_read=256 << 10, mem_high_watermark=None, mem_low_watermark=None,
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
-                 persist_group_ms=2.0, exchange_bindings=False):
+                 persist_group_ms=2.0, exchange_bindings=False, headers_match=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -229,6 +229,12 @@ class GpuBroker:
         # Exchange.Bind / Exchange.Unbind (exchange-to-exchange bindings, routed by the data
         # plane's closure walk): served and advertised when on, 540 NOT_IMPLEMENTED when off
         self.exchange_bindings = bool(exchange_bindings)
+        # headers exchanges matched on their bindings' arguments (chana.mq.gpu.headers-match):
+        # the plane does the matching (built with headers_match=True); the broker passes
+        # Queue.Bind / Queue.Unbind (and Exchange.Bind / Unbind) arguments on only when it is on
+        self.headers_match = bool(headers_match)
+        if self.headers_match and not getattr(plane, "headers_match", False):
+            raise ValueError("headers_match=True needs a data plane built with headers_match=True")
         native_x = bool(getattr(plane, "native_xchg", False))
         if io == "auto":
             io = "pipeline" if (hasattr(plane, "eng") and (node is None or native_x)) else "native"
@@ -761,7 +767,7 @@ class GpuBroker:
         elif op == "delete_queue":
             ps.queue_deleted(args[0], args[1])
         elif op == "bind":
-            ps.bind(*args[:4])
+            ps.bind(*args[:4])        # (the row is written from the plane's bindings: no arguments needed)
         elif op == "unbind":
             ps.unbind(*args[:4])
 
@@ -1477,6 +1483,11 @@ class GpuBroker:
         expire_ms = now + int(exp) if isinstance(exp, str) and exp.isdigit() else 0
         return now, flags, expire_ms, ts_ms
 
+    def _bind_args(self, m):
+        """The arguments of a Queue.Bind / Unbind / Exchange.Bind / Unbind as the plane takes
+        them: passed on with headers-match on, dropped (as always before) with it off."""
+        return dict(m.arguments or {}) if self.headers_match else None
+
     def _big_sharded(self, c, b, rest):
         """Sharded node: the queues the publish routes to may live on any rank.  Routed on
         the host over the replicated bindings, the message goes out as a control-log op
@@ -1488,7 +1499,7 @@ class GpuBroker:
         p, m, ch = self.plane, b["m"], b["ch"]
         x = b["x"]
         targets = {}
-        for slot in p.route_host(x, m.routing_key.encode()):
+        for slot in p.route_host(x, m.routing_key.encode(), bytes(b["props_raw"])):
             q = p.queue_by_slot.get(slot)
             if q is not None:
                 targets.setdefault(int(q.owner), []).append(int(slot))
@@ -1612,23 +1623,24 @@ class GpuBroker:
                                          consumer_count=len(qq.consumers)))
         elif n == "queue.bind":
             qn = m.queue or c.last_queue.get(ch, "")
-            p.bind(vh, qn, m.exchange, m.routing_key)
+            p.bind(vh, qn, m.exchange, m.routing_key, self._bind_args(m))
             if self.persistence is not None:
                 self.persistence.bind(vh, qn, m.exchange, m.routing_key)
             if not m.nowait:
                 self._send(c, ch, Method("queue.bind_ok"))
         elif n == "queue.unbind":
             qn = m.queue or c.last_queue.get(ch, "")
-            p.unbind(vh, qn, m.exchange, m.routing_key)
+            p.unbind(vh, qn, m.exchange, m.routing_key, self._bind_args(m))
             if self.persistence is not None:
                 self.persistence.unbind(vh, qn, m.exchange, m.routing_key)
             self._send(c, ch, Method("queue.unbind_ok"))
         elif n in _EDGE_METHODS and self.exchange_bindings:
-            # (arguments are accepted and ignored; edges are not written to the store)
+            # (arguments count for a headers source with headers-match on, and are ignored
+            # otherwise; edges are not written to the store)
             if n == "exchange.bind":
-                p.bind_exchange(vh, m.destination, m.source, m.routing_key)
+                p.bind_exchange(vh, m.destination, m.source, m.routing_key, self._bind_args(m))
             else:
-                p.unbind_exchange(vh, m.destination, m.source, m.routing_key)
+                p.unbind_exchange(vh, m.destination, m.source, m.routing_key, self._bind_args(m))
             if not m.nowait:
                 self._send(c, ch, Method(n + "_ok"))
         elif n == "queue.purge":
@@ -1783,12 +1795,13 @@ class GpuBroker:
             reply = None if m.nowait else reply
         elif n in ("queue.bind", "queue.unbind"):
             qn = m.queue or c.last_queue.get(ch, "")
-            seq = node.submit("bind" if n == "queue.bind" else "unbind", vh, qn, m.exchange, m.routing_key)
+            seq = node.submit("bind" if n == "queue.bind" else "unbind", vh, qn, m.exchange, m.routing_key,
+                              self._bind_args(m))
             ok = "queue.bind_ok" if n == "queue.bind" else "queue.unbind_ok"
             reply = None if (n == "queue.bind" and m.nowait) else (lambda r, ok=ok: Method(ok))
         elif n in _EDGE_METHODS:
             seq = node.submit("bind_exchange" if n == "exchange.bind" else "unbind_exchange", vh, m.destination,
-                              m.source, m.routing_key)
+                              m.source, m.routing_key, self._bind_args(m))
             reply = None if m.nowait else (lambda r, ok=n + "_ok": Method(ok))
         else:   # queue.delete
             q = self._queue(vh, m.queue or c.last_queue.get(ch, ""), 50, 40)

@@ -282,6 +282,12 @@ class Config:
         if store_dir:
             plane.update(persist=1, persist_max=int(g(k + "persist-records", 1 << 16)),
                          persist_bytes=int(g(k + "persist-bytes", 256 << 20)))
+        # headers exchanges matched on their bindings' arguments (off: they route as topic);
+        # headers-bindings / headers-pairs bound the device's row table and pair pool
+        headers_match = bool(g(k + "headers-match", False))
+        if headers_match:
+            hb = int(g(k + "headers-bindings", 1024))
+            plane.update(headers_match=True, hb_max=hb, hp_max=int(g(k + "headers-pairs", 4 * hb)))
         hi = int(g("chana.mq.flow.memory-high-watermark", -1))
         lo = int(g("chana.mq.flow.memory-low-watermark", -1))
         if hi < 0:   # 40% of what the broker can hold: the HBM body log + the host spill ring
@@ -293,6 +299,7 @@ class Config:
                       confirm_read=int(g(k + "confirm-read", 128 << 10)),
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
+                      headers_match=headers_match,
                       mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 

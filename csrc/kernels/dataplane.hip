@@ -155,6 +155,7 @@ __global__ __launch_bounds__(1024) void k_stage(DS d) {
 }
 
 #include "dp_frame_scan.h"
+#include "dp_headers.h"
 
 // ============================================================================ K3 classify / decode
 DEV void set_counts(const DS& d, u32 np, u32 na) {
@@ -1233,7 +1234,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
       __shared__ u32 hop_list[16][HOP_QMAX];   // (route pass 0 runs at most 16 waves per block)
       h.L = hop_list[threadIdx.x >> 6];
       h.visited = (x >> 5) == lane ? 1u << (x & 31) : 0u;
-      xt &= XF_TYPE;
+      xt &= XF_TYPE | XF_HMATCH;
     }
     for (;;) {
       if (xt == EX_DIRECT || xt == EX_FANOUT) {
@@ -1263,6 +1264,33 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
           for (u32 k0 = 0; k0 < xc; k0 += 64) {
             const bool v = k0 + lane < xc;
             hop_add(h, v ? (xl[xo + k0 + lane] | XT_EDGE) : 0u, v, lane);
+          }
+        }
+      } else if (PASS == 0 && __builtin_expect(hop && (xt & XF_HMATCH) != 0, 0)) {
+        // headers, matched on the bindings' arguments against the publish's own property bytes
+        // (an imported record's lie in recv_pay): a row per lane, a queue taken once by its
+        // first hit as with the topic rows.  Always as a walk (the host sets XF_HOP with
+        // XF_HMATCH, edges or none): the queues go through the walk's list, and above PUB_QC
+        // of them into hop_q, so pass 1 never matches again and k_route_store holds no
+        // headers code.  (The table is opened and checked again for every 64 rows: opened once
+        // in front of this loop, its bounds stay live across hop_add and k_route spills 11
+        // VGPRs to scratch -- profiles/headers_match/resource_usage.md)
+        if constexpr (PASS == 0) {
+          const u32 o = d.x_h_off[x], c = d.x_h_n[x];
+          const u8* props = pub_src(d, pb) + hdr_s(pb.props_off);
+          const u32 plen = hdr_s(pb.props_len);
+          u32 lastq = INVALID;
+          for (u32 k0 = 0; k0 < c; k0 += 64) {
+            const bool v = k0 + lane < c;
+            const u32 r = o + k0 + lane;
+            const u32 q = v ? d.h_queue[r] : INVALID;
+            const bool hit = headers_hit(props, plen, d.h_meta, d.h_pair, d.hp, d.kpool, r, v, lane);
+            const u64 hm = __ballot(hit);
+            const u64 below = hm & lanemask_lt();
+            const u32 qb = (u32)__shfl((int)q, below ? 63 - __clzll(below) : 0);
+            const u32 qtop = (u32)__shfl((int)q, hm ? 63 - __clzll(hm) : 0);
+            hop_add(h, q, hit && (below ? qb : lastq) != q, lane);
+            if (hm) lastq = qtop;
           }
         }
       } else {
@@ -1296,7 +1324,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
         }
       }
       if (__builtin_expect(!hop, 1) || !hop_next(h, x, lane)) break;
-      xt = d.x_type[x] & XF_TYPE;
+      xt = d.x_type[x] & (XF_TYPE | XF_HMATCH);
     }
     if constexpr (PASS == 0) {
       if (hop) hop_finish(d, a, h, pb, p, srank, lane);

@@ -30,10 +30,15 @@ enum : u32 { EX_DIRECT = 0, EX_FANOUT = 1, EX_TOPIC = 2, EX_HEADERS = 3 };
 // has outgoing edges; a publish entering there walks the closure on the device (route_hop)
 enum : u32 {
   XF_TYPE = 0xff, XF_HOP = 0x100,
+  XF_HMATCH = 0x200,       // a headers exchange matched on its bindings' arguments (dp_headers.h; without it
+                           // a headers exchange routes as topic)
   XT_EDGE = 0x80000000u,   // t_queue of a topic row that is an edge: destination exchange slot below
   HOP_XSLOTS = 2048,       // exchanges taking part in an edge: slot below this (one bit per slot, 32 per lane)
   HOP_QMAX = 1024          // distinct queues a walk can reach (per-wave LDS list; enforced at bind time)
 };
+// ---- headers bindings (dp_headers.h): pairs of one binding (a row lane keeps a seen and a hit bit
+// per pair, and walks its pairs once per message entry); words of a pair in the pair pool
+enum : u32 { HB_PAIRS = 16, HP_WORDS = 6 };
 
 
 // ---- message flags

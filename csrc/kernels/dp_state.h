@@ -361,4 +361,11 @@ struct DS {
   u32 lk_cap;
   u32* lk_cnt;              // [WORLD_MAX] acks packed this step
   const AckRec* rack;       // acks received for this step (contiguous, all sources)
+
+  // ---------------- headers exchanges matched on arguments (x_type & XF_HMATCH; dp_headers.h)
+  u32* x_h_off; u32* x_h_n; // [x_max] the exchange's rows
+  u32* h_queue;             // [hb_max] queue slot, or XT_EDGE | destination (rows sorted by it, edges last)
+  u32* h_meta;              // [hb_max] pairs | HM_ANY
+  u32* h_pair;              // [hb_max] first pair in hp
+  u32* hp;                  // [hp_max][HP_WORDS] pair pool
 };

@@ -226,6 +226,8 @@ class Engine {
     d_.dhash_mask = dhash - 1;
     d_.tb_max = (u32)get("tb_max", 4096);
     d_.tb_pad = ((d_.tb_max + 15) / 16) * 16;
+    hb_max_ = std::max<u32>(1, (u32)get("hb_max", 1024));          // headers binding rows (chana.mq.gpu.headers-bindings)
+    hp_max_ = std::max<u32>(1, (u32)get("hp_max", 4ull * hb_max_));  // pairs of all of them
     d_.req_max = (u32)get("req_max", 65536);
     d_.hash_wildcard = (u32)get("hash_wildcard", 1);
     d_.frame_max_global = (u32)get("frame_max", 131072);
@@ -266,6 +268,7 @@ class Engine {
     hopx_max_ = (u32)get("hopx_max", 1u << 16);   // exchange-to-exchange edges per source type (like fan_max)
     const u32 hopx_max = hopx_max_;
     u64 kpool = get("kpool", 16ull << 20);
+    kpool_ = kpool;
     u32 nch = d_.c_max * d_.chpc;
     // pair key = queue << 1 | (source rank >= this rank) at world > 1: the pairs are
     // generated as (this rank's publishes, then imports in source-rank order) and the sort
@@ -452,6 +455,12 @@ class Engine {
     d_.t_expect = (i32*)dev("t_expect", 4ull * d_.tb_pad);
     d_.t_mat = (i8*)dev("t_mat", (u64)d_.tb_pad * TOPIC_K + 64);
     d_.t_woff = (u16*)dev("t_woff", 2ull * TOPIC_WORDS * d_.tb_pad + 64);
+    d_.x_h_off = (u32*)dev("x_h_off", 4ull * d_.x_max);
+    d_.x_h_n = (u32*)dev("x_h_n", 4ull * d_.x_max);
+    d_.h_queue = (u32*)dev("h_queue", 4ull * hb_max_);
+    d_.h_meta = (u32*)dev("h_meta", 4ull * hb_max_);
+    d_.h_pair = (u32*)dev("h_pair", 4ull * hb_max_);
+    d_.hp = (u32*)dev("hp", 4ull * HP_WORDS * hp_max_);
 
     d_.q_ring_off = (u64*)dev("q_ring_off", 8ull * d_.q_max);
     d_.q_ring_mask = (u64*)dev("q_ring_mask", 8ull * d_.q_max);
@@ -926,6 +935,7 @@ class Engine {
     o["chmap_size"] = d_.chmap_size; o["xhash"] = d_.xhash_mask + 1; o["dhash"] = d_.dhash_mask + 1;
     o["tb_max"] = d_.tb_max; o["tb_pad"] = d_.tb_pad; o["log_bytes"] = d_.log_bytes;
     o["spill_bytes"] = d_.spill_bytes;
+    o["hb_max"] = hb_max_; o["hp_max"] = hp_max_; o["hb_pairs"] = (u32)HB_PAIRS; o["kpool"] = kpool_;
     o["hop_qmax"] = (u32)HOP_QMAX; o["hop_xslots"] = (u32)HOP_XSLOTS; o["hopx_max"] = hopx_max_;
     o["ingress_cap"] = d_.ingress_cap; o["egress_cap"] = d_.egress_cap; o["ring_pool"] = d_.ring_pool;
     o["work_cap"] = d_.work_cap; o["total_bytes"] = total_bytes_; o["req_max"] = d_.req_max;
@@ -980,6 +990,8 @@ class Engine {
   bool sdma_ = true;       // copy_engine 1: NoCU copy requests
   u32 copy_wgs_ = 16;
   u32 hopx_max_ = 1u << 16;   // capacity of fan_x / d_x (cfg hopx_max)
+  u32 hb_max_ = 1024, hp_max_ = 4096;   // headers rows / pair pool (cfg hb_max, hp_max)
+  u64 kpool_ = 0;             // key pool bytes (cfg kpool)
   int sdma_pref_ = -1, sdma_split_ = 1;
   bool gated_ = false;     // egress D2H queued at launch behind a gate (HSA SDMA)
   bool h2d_hsa_ = false;   // ingress payloads in GPU-mapped host memory go to an SDMA engine through HSA
@@ -2827,6 +2839,7 @@ PYBIND11_MODULE(_dataplane, m) {
   m.attr("RS_RT") = RS_RT;
   m.attr("RS_RB") = RS_RB;
   m.attr("PUB_QC") = PUB_QC;
+  m.attr("HB_PAIRS") = (u32)HB_PAIRS;   // pairs of one headers binding (dp_headers.h)
   m.attr("SORT_ONEPASS_BITS") = SORT_ONEPASS_BITS;
   m.attr("LAT_BINS") = LAT_BINS;
   m.attr("DVW_LDS") = DVW_LDS;   // the delivery layout / render limits (dataplane.hip)
