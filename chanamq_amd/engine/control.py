@@ -9,6 +9,7 @@ dense device tables built from it.
 """
 
 from dataclasses import dataclass, field
+from typing import Optional
 
 from ..protocol import constants as C
 
@@ -63,6 +64,10 @@ class Queue:
     owner: int = 0                                  # owning rank (sharded data plane)
     requested: int = 0                              # requested ring capacity (for re-homing)
     max_capacity: int = 0                           # ring growth limit (0 = the ring pool)
+    # x-max-length / x-overflow (queue_limits on): at most max_length ready messages (None: no
+    # limit); "drop-head" trims the head at the end of a step, "reject-publish" refuses at enqueue
+    max_length: Optional[int] = None
+    overflow: str = "drop-head"
 
 
 @dataclass
@@ -124,7 +129,10 @@ class ControlState:
 
     def __init__(self, c_max=1024, chpc=16, q_max=4096, x_max=1024, cons_max=16384,
                  hash_wildcard=True, ring_pool=1 << 26, default_queue_capacity=1 << 16,
-                 world=1, rank=0, shard_map=None, headers_match=False):
+                 world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False):
+        # chana.mq.gpu.queue-limits: a queue's x-max-length / x-overflow are honoured (off: they
+        # are ignored, as the reference does)
+        self.queue_limits = bool(queue_limits)
         # chana.mq.gpu.headers-match: a headers exchange matches on its bindings' arguments
         # (off: it routes as topic and arguments are ignored, as the reference does)
         self.headers_match = bool(headers_match)
@@ -282,10 +290,24 @@ class ControlState:
         return off
 
     def declare_queue(self, vhost, name, durable=False, exclusive_owner=-1, auto_delete=False,
-                      ttl_ms=0, capacity=None, passive=False, max_capacity=0):
+                      ttl_ms=0, capacity=None, passive=False, max_capacity=0, max_length=None, overflow="drop-head"):
         key = (vhost, name)
         q = self.queues.get(key)
+        if not self.queue_limits:
+            max_length = None
+        elif max_length is not None:
+            max_length, overflow = self.check_limit(max_length, overflow)
         if q is not None:
+            # a declare of an existing queue returns its slot; with queue_limits on, a limit that
+            # differs from the queue's is refused, but a queue without one (a recovered durable
+            # queue: the store keeps no limit) adopts that of the first declare that carries one
+            if max_length is not None and not passive:
+                if q.max_length is None:
+                    q.max_length, q.overflow = max_length, overflow
+                    self.queue_limit_changed(q)
+                elif (q.max_length, q.overflow) != (max_length, overflow):
+                    raise ControlError(C.PRECONDITION_FAILED, f"queue '{name}' is declared with x-max-length "
+                                       f"{q.max_length} ({q.overflow})", 50, 10)
             return q.slot
         if passive:
             raise ControlError(C.NOT_FOUND, f"no queue '{name}' in vhost '{vhost}'", 50, 10)
@@ -298,7 +320,8 @@ class ControlState:
             cap <<= 1
         slot = self._free_q.pop()
         q = Queue(slot, vhost, name, durable, exclusive_owner, auto_delete, ttl_ms, cap,
-                  self._ring_alloc(cap), owner=owner, requested=capacity, max_capacity=max_capacity)
+                  self._ring_alloc(cap), owner=owner, requested=capacity, max_capacity=max_capacity,
+                  max_length=max_length, overflow=overflow if max_length is not None else "drop-head")
         self.queues[key] = q
         self.queue_by_slot[slot] = q
         dx = self.exchanges.get((vhost, ""))
@@ -307,6 +330,28 @@ class ControlState:
         self.queue_declared(q)
         self.routing_changed()
         return slot
+
+    OVERFLOW_MODES = ("drop-head", "reject-publish")
+    MAX_LENGTH_TOP = 0x7ffffffe   # what the device's q_limit word holds (a larger limit bounds nothing)
+
+    @classmethod
+    def check_limit(cls, max_length, overflow="drop-head"):
+        """(max_length, overflow) as a queue keeps them, or 406 PRECONDITION_FAILED: the length an
+        integer >= 0, the mode one of the two served."""
+        if isinstance(max_length, bool) or not isinstance(max_length, int) or max_length < 0:
+            raise ControlError(C.PRECONDITION_FAILED, f"invalid x-max-length {max_length!r}", 50, 10)
+        if overflow is None:
+            overflow = "drop-head"
+        if overflow not in cls.OVERFLOW_MODES:
+            raise ControlError(C.PRECONDITION_FAILED, f"invalid x-overflow {overflow!r}", 50, 10)
+        return min(max_length, cls.MAX_LENGTH_TOP), overflow
+
+    def set_queue_limit(self, slot, max_length, overflow="drop-head"):
+        """Queue ``slot``'s limit as given (None: none), on this plane only: a reload lifts the
+        limit while it restores the queue's messages and puts it back afterwards."""
+        q = self.queue_by_slot[slot]
+        q.max_length, q.overflow = max_length, (overflow if max_length is not None else "drop-head")
+        self.queue_limit_changed(q)
 
     def grow_target(self, q, depth):
         """Ring capacity for a queue holding ``depth`` entries once it passed half its ring:
@@ -677,4 +722,5 @@ class ControlState:
     def channel_closing(self, chan): ...
     def queue_declared(self, q): ...
     def queue_deleted(self, q): ...
+    def queue_limit_changed(self, q): ...
     def consumers_changed(self, q, cid, removed=False): ...

@@ -72,8 +72,11 @@ class StepResult:
 class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
                  world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
-                 headers_match=False, **cfg):
-        """``headers_match``: headers exchanges match on their bindings' arguments (the
+                 headers_match=False, queue_limits=False, **cfg):
+        """``queue_limits``: queues honour x-max-length / x-overflow (q_limit: trim_head in
+        k_dequeue, the refusal in enq_store).  Off: the device never reads the field.
+
+        ``headers_match``: headers exchanges match on their bindings' arguments (the
         headers branch of route_one; engine cfg hb_max / hp_max bound its tables).  Off: they
         route as topic.
 
@@ -100,7 +103,7 @@ class GpuDataPlane(ControlState):
             full.setdefault("overlap", 0)
             full.setdefault("copy_engine", 3)
         full.update(device=device, hash_wildcard=int(hash_wildcard), graph=int(graph), world=world, rank=rank,
-                    exchange_lag=int(exchange_lag))
+                    exchange_lag=int(exchange_lag), queue_limits=int(bool(queue_limits)))
         self.eng = self.mod.Engine(full)
         self.info = self.eng.info()
         sz = self.info["sizeof"]
@@ -155,7 +158,7 @@ class GpuDataPlane(ControlState):
         super().__init__(c_max=i["c_max"], chpc=i["chpc"], q_max=i["q_max"], x_max=i["x_max"],
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
-                         shard_map=shard_map, headers_match=headers_match)
+                         shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits)
 
     # ================================================================== uploads
     # ``defer`` (set by the broker around control work done while steps keep running): table
@@ -456,10 +459,20 @@ class GpuDataPlane(ControlState):
         self._up_at("q_head", 0, q.slot, np.uint64)
         self._up_at("q_tail", 0, q.slot, np.uint64)
         self._up_at("q_ttl", q.ttl_ms, q.slot, np.int64)
+        if self.queue_limits:
+            self.queue_limit_changed(q)
         self._up_at("q_rr", 0, q.slot, np.uint32)
         self._up_at("req_q_n", 0, q.slot, np.uint32)
         self._up_at("q_active", 1, q.slot, np.uint32)
         self._sync_consumers()
+
+    def queue_limit_changed(self, q):
+        # q_limit (dp_state.h): 0 = no limit, else (L + 1) | QL_REJECT; a queue owned by another
+        # rank holds nothing here (its owner enforces the limit)
+        ql = 0
+        if q.max_length is not None and q.owner == self.rank:
+            ql = (min(int(q.max_length), self.MAX_LENGTH_TOP) + 1) | (0x80000000 if q.overflow == "reject-publish" else 0)
+        self._up_at("q_limit", ql, q.slot, np.uint32)
 
     def queue_deleted(self, q):
         self._up_at("q_active", 0, q.slot, np.uint32)

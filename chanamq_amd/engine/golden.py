@@ -750,6 +750,15 @@ class GoldenDataPlane(ControlState):
         for q in qs:
             qq = self.queue_by_slot[q]
             ring = self.ring[q]
+            if self.queue_limits and qq.max_length is not None and qq.overflow == "reject-publish" \
+                    and len(ring) >= qq.max_length:
+                # x-max-length, reject-publish (enq_store): refused like a full ring, counted apart;
+                # requeues may have put the depth above the limit (plan_queue grows no ring for these)
+                cnt["n_maxlen_rejected"] += 1
+                self._release(msg)
+                if chslot is not None:
+                    self.ch[chslot]["pub_fail"] = True
+                continue
             if len(ring) >= qq.capacity:   # the device grows the ring before enqueueing (k_ring_plan)
                 new = self.grow_target(qq, len(ring) + 1)
                 if new is not None:
@@ -817,13 +826,22 @@ class GoldenDataPlane(ControlState):
         ring = self.ring[q]
         cnt = self.counters
         budget_q = self.persist and qq.durable
+        # queue_limits on: the device's reservations one for one, because the trim at the end of
+        # the queue's step draws on what they leave -- the walk reserves 64 records per iteration,
+        # the iteration that finds a live entry at the head included.  With the option off the
+        # walk keeps its older accounting (a reservation only for an expired head), which is
+        # knowingly inexact: it differs from the device only in how soon a budget shared by many
+        # durable queues runs out, and changing it is left to a change of its own
+        exact = self.queue_limits and budget_q
         left = 0
-        while ring and ring[0][2] and ring[0][2] <= now_ms:
+        while ring and (exact or (ring[0][2] and ring[0][2] <= now_ms)):
             if budget_q and not left:   # reserved 64 at a time (dataplane.hip k_dequeue)
                 if self._ttl_budget + 64 > self.persist_max >> 2:
                     break
                 self._ttl_budget += 64
                 left = 64
+            if not (ring[0][2] and ring[0][2] <= now_ms):
+                break
             left -= 1
             self._consumed(ring[0][0], q, self.qpos_head[q], 1)
             self._release(ring.pop(0)[0])
@@ -852,6 +870,7 @@ class GoldenDataPlane(ControlState):
             self.qpos_head[q] += 1
         mall = len(qq.consumers)
         if not mall or not ring:
+            self._trim(q, qq, ring)
             return got
         m = min(mall, 64 - len(got))
         r = self.qrr[q] % mall
@@ -902,7 +921,27 @@ class GoldenDataPlane(ControlState):
         self.qrr[q] = (r + 1) % mall
         del ring[:pos]
         self.qpos_head[q] += pos
+        self._trim(q, qq, ring)
         return got + out
+
+    def _trim(self, q, qq, ring):
+        """x-max-length, drop-head (trim_head in k_dequeue): at the end of the queue's step --
+        after its enqueue, requeues, TTL walk, Basic.Gets and dispatch -- the ready entries above
+        the limit leave from the head like expired ones, 64 an iteration; a durable queue on a
+        persisting plane draws on the TTL walk's record budget and goes on in the next steps."""
+        if not self.queue_limits or qq.max_length is None or qq.overflow != "drop-head":
+            return
+        budget_q = self.persist and qq.durable
+        while len(ring) > qq.max_length:
+            if budget_q:
+                if self._ttl_budget + 64 > self.persist_max >> 2:
+                    break
+                self._ttl_budget += 64
+            for _ in range(min(64, len(ring) - qq.max_length)):
+                self._consumed(ring[0][0], q, self.qpos_head[q], 1)
+                self._release(ring.pop(0)[0])
+                self.qpos_head[q] += 1
+                self.counters["n_maxlen_dropped"] += 1
 
     def set_deliver_cap_bytes(self, n):
         self.deliver_cap_bytes = int(n)

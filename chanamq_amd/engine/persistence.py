@@ -207,6 +207,26 @@ class GpuPersistence:
         else:
             self.store.delete_bind(entity_id(vhost, exchange), entity_id(vhost, queue), key)
 
+    def _reload(self, items, now_ms):
+        """Restore ``items`` with their queues' length limits lifted (queue-limits on: a reload is
+        never refused by reject-publish) and put back afterwards: a drop-head queue that came
+        back above its limit trims at its next step."""
+        if not items:
+            return 0
+        p = self.plane
+        held = []
+        if getattr(p, "queue_limits", False):
+            for slot in sorted({it[0] for it in items}):
+                q = p.queue_by_slot.get(slot)
+                if q is not None and q.max_length is not None:
+                    held.append((slot, q.max_length, q.overflow))
+                    p.set_queue_limit(slot, None)
+        try:
+            return p.restore(items, now_ms)
+        finally:
+            for slot, length, mode in held:
+                p.set_queue_limit(slot, length, mode)
+
     # ------------------------------------------------------------------ failover
     def adopt(self, src, queues, now_ms=None):
         """HA failover: this rank now owns ``queues`` (Queue objects re-homed
@@ -255,7 +275,7 @@ class GpuPersistence:
                     self.rows[(qid, mid)] = [base + i, len(body), False]
                 else:
                     seeds.append((qid, mid, base + i, len(body)))
-        n = p.restore(items, now_ms) if items else 0
+        n = self._reload(items, now_ms)
         st.sync()
         for qid, mid, off, size in seeds:
             self.native.seed_row(qid, mid, off, size, False, adopt_refs[mid])
@@ -329,7 +349,7 @@ class GpuPersistence:
             if (v, q) in p.queues:
                 for cargs in args_from_map(amap):   # (one binding, without arguments, unless headers-match wrote it)
                     p.bind(v, q, x, key, cargs)
-        n = p.restore(items, now_ms) if items else 0
+        n = self._reload(items, now_ms)
         # new ids strictly above every stored one (snowflake ms field), even if the device
         # clock ran ahead of the wall clock before the restart or the clock went back
         top = max((it[1] for it in items), default=0)

@@ -40,7 +40,7 @@ import numpy as np
 from ..engine.control import ControlError, normalize_vhost
 from ..engine.layout import MF_HAS_TS, MF_PERSIST, SS_FRAME_ERROR, SS_OVERFLOW, SS_TOO_LARGE, SS_UNEXPECTED
 from ..protocol import constants as C
-from ..protocol.codec import (Method, decode_content_header, decode_method, encode_method_frame, encode_table,
+from ..protocol.codec import (Method, Typed, decode_content_header, decode_method, encode_method_frame, encode_table,
                               render_command)
 
 HEARTBEAT = C.HEARTBEAT_FRAME
@@ -219,7 +219,7 @@ class GpuBroker:
                  ingress_bytes=64 << 20, per_conn_read=256 << 10, mem_high_watermark=None, mem_low_watermark=None,
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
-                 persist_group_ms=2.0, exchange_bindings=False, headers_match=False):
+                 persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -235,6 +235,12 @@ class GpuBroker:
         self.headers_match = bool(headers_match)
         if self.headers_match and not getattr(plane, "headers_match", False):
             raise ValueError("headers_match=True needs a data plane built with headers_match=True")
+        # queue length limits (chana.mq.gpu.queue-limits): Queue.Declare's x-max-length / x-overflow
+        # are parsed and passed to the plane (built with queue_limits=True, which enforces them);
+        # off, they are ignored as always before
+        self.queue_limits = bool(queue_limits)
+        if self.queue_limits and not getattr(plane, "queue_limits", False):
+            raise ValueError("queue_limits=True needs a data plane built with queue_limits=True")
         native_x = bool(getattr(plane, "native_xchg", False))
         if io == "auto":
             io = "pipeline" if (hasattr(plane, "eng") and (node is None or native_x)) else "native"
@@ -343,6 +349,8 @@ class GpuBroker:
         self._running = False
         self._wake_r, self._wake_w = os.pipe()
         self.stats = dict(steps=0, published=0, delivered=0, connections=0)
+        if self.queue_limits:
+            self.stats.update(maxlen_dropped=0, maxlen_rejected=0)
         self.lock = _PlaneLock(self)
         self.light = _LightLock(self.lock)
 
@@ -802,6 +810,8 @@ class GpuBroker:
             return
         st = self.fe.stats()
         self.stats.update(steps=st["steps"], published=st["published"], delivered=st["delivered"])
+        if self.queue_limits:
+            self.stats.update(maxlen_dropped=st.get("maxlen_dropped", 0), maxlen_rejected=st.get("maxlen_rejected", 0))
         if st.get("spill_moved"):
             self.stats["spilled_bytes"] = st["spill_moved"]
         self._fe_stats = st
@@ -1224,6 +1234,9 @@ class GpuBroker:
         self.stats["steps"] += 1
         self.stats["published"] += cnt.get("n_pubs", 0)
         self.stats["delivered"] += cnt.get("n_deliv", 0)
+        if self.queue_limits:   # x-max-length: trimmed from drop-head queues / refused by reject-publish queues
+            self.stats["maxlen_dropped"] += cnt.get("n_maxlen_dropped", 0)
+            self.stats["maxlen_rejected"] += cnt.get("n_maxlen_rejected", 0)
         for conn, code, chslot in events:
             c = self.conns.get(conn)
             if c is None or c.state != "open":
@@ -1483,6 +1496,31 @@ class GpuBroker:
         expire_ms = now + int(exp) if isinstance(exp, str) and exp.isdigit() else 0
         return now, flags, expire_ms, ts_ms
 
+    def _limit_args(self, m, q=None):
+        """Queue.Declare's x-max-length / x-overflow as ``declare_queue`` keywords, with
+        queue-limits on ({} with it off, or without a limit: the arguments are ignored as always
+        before; x-max-length-bytes stays ignored).  A length that is no integer >= 0, or a mode
+        other than drop-head / reject-publish, is 406 PRECONDITION_FAILED with nothing changed.
+        ``q`` (the sharded submit only, which must refuse before anything is replicated): the
+        existing queue, whose limit the declare must not differ from; on a single node
+        ``ControlState.declare_queue`` alone holds that rule."""
+        if not self.queue_limits:
+            return {}
+        args = m.arguments or {}
+        ov = args.get("x-overflow")
+        if ov is not None and ov not in self.plane.OVERFLOW_MODES:
+            raise ControlError(C.PRECONDITION_FAILED, f"invalid x-overflow {ov!r}", 50, 10)
+        if "x-max-length" not in args:
+            return {}
+        v = args["x-max-length"]
+        if isinstance(v, Typed) and v.tag in "bBsuIil":
+            v = v.value
+        length, ov = self.plane.check_limit(v, ov)
+        if q is not None and not m.passive and q.max_length is not None and (q.max_length, q.overflow) != (length, ov):
+            raise ControlError(C.PRECONDITION_FAILED, f"queue '{q.name}' is declared with x-max-length "
+                               f"{q.max_length} ({q.overflow})", 50, 10)
+        return dict(max_length=length, overflow=ov)
+
     def _bind_args(self, m):
         """The arguments of a Queue.Bind / Unbind / Exchange.Bind / Unbind as the plane takes
         them: passed on with headers-match on, dropped (as always before) with it off."""
@@ -1612,7 +1650,7 @@ class GpuBroker:
             if q is not None and q.exclusive_owner not in (-1, c.id):
                 raise ControlError(C.RESOURCE_LOCKED, f"queue '{name}' is exclusive to another connection", 50, 10)
             slot = p.declare_queue(vh, name, durable=m.durable, exclusive_owner=c.id if m.exclusive else -1,
-                                   auto_delete=m.auto_delete, ttl_ms=ttl, passive=m.passive)
+                                   auto_delete=m.auto_delete, ttl_ms=ttl, passive=m.passive, **self._limit_args(m))
             c.last_queue[ch] = name
             if self.persistence is not None and q is None and not m.passive:
                 self.persistence.queue(p.queue_by_slot[slot])
@@ -1781,11 +1819,12 @@ class GpuBroker:
                 cnt = p.message_count(q.slot) if q.owner == p.rank else 0
                 return self._send(c, ch, Method("queue.declare_ok", queue=name, message_count=cnt,
                                                 consumer_count=len(q.consumers)))
+            args = m.arguments or {}
+            lim = self._limit_args(m, q)   # (406 before anything is submitted; every replica applies the rule)
             if q is None:   # client-local placement: the queue lives on the declaring rank
                 node.submit("place_queue", vh, name, p.rank)
-            args = m.arguments or {}
             seq = node.submit("declare_queue", vh, name, durable=m.durable, auto_delete=m.auto_delete,
-                              ttl_ms=int(args.get("x-message-ttl", 0) or 0))
+                              ttl_ms=int(args.get("x-message-ttl", 0) or 0), **lim)
             c.last_queue[ch] = name
 
             def reply(r, name=name):

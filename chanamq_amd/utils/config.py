@@ -288,6 +288,10 @@ class Config:
         if headers_match:
             hb = int(g(k + "headers-bindings", 1024))
             plane.update(headers_match=True, hb_max=hb, hp_max=int(g(k + "headers-pairs", 4 * hb)))
+        # queues honour Queue.Declare's x-max-length / x-overflow (off: the arguments are ignored)
+        queue_limits = bool(g(k + "queue-limits", False))
+        if queue_limits:
+            plane.update(queue_limits=True)
         hi = int(g("chana.mq.flow.memory-high-watermark", -1))
         lo = int(g("chana.mq.flow.memory-low-watermark", -1))
         if hi < 0:   # 40% of what the broker can hold: the HBM body log + the host spill ring
@@ -299,7 +303,7 @@ class Config:
                       confirm_read=int(g(k + "confirm-read", 128 << 10)),
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
-                      headers_match=headers_match,
+                      headers_match=headers_match, queue_limits=queue_limits,
                       mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 

@@ -322,6 +322,7 @@ PYBIND11_MODULE(_core, m) {
              o["live_bytes"] = s.live_bytes; o["live_msgs"] = s.live_msgs; o["io_phase_s"] = s.io_phase_s;
              o["dropped_nomem"] = s.dropped_nomem; o["ring_full"] = s.ring_full; o["unroutable"] = s.unroutable;
              o["routed"] = s.routed; o["expired"] = s.expired; o["ctrl"] = s.ctrl; o["log_used"] = s.log_used;
+             o["maxlen_dropped"] = s.maxlen_dropped; o["maxlen_rejected"] = s.maxlen_rejected;
              o["wait_s"] = s.wait_s;
              o["submit_s"] = s.submit_s;
              o["xchg_s"] = s.xchg_s; o["xchg_steps"] = s.xchg_steps; o["syncs"] = s.syncs;

@@ -1300,6 +1300,8 @@ void Frontend::finish_oldest(std::deque<Inflight>& inflight) {
     stats_.unroutable += c.n_unroutable;
     stats_.routed += c.n_routed_msgs;
     stats_.expired += c.n_expired;
+    stats_.maxlen_dropped += c.n_maxlen_dropped;
+    stats_.maxlen_rejected += c.n_maxlen_rejected;
     stats_.ctrl += c.n_ctrl;
     stats_.live_msgs = c.n_live_msgs;
     stats_.log_used = c.log_head - c.log_tail;

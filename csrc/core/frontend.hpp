@@ -108,6 +108,7 @@ struct FeStats {
   u64 held_steps = 0, idle_steps = 0, gather_segs = 0;
   u64 store_fail_nacks = 0;   // publisher confirms turned into Basic.Nack: their store commit failed
   u64 dropped_nomem = 0, ring_full = 0, unroutable = 0, routed = 0, expired = 0, ctrl = 0;
+  u64 maxlen_dropped = 0, maxlen_rejected = 0;   // x-max-length: trimmed from queue heads / publishes refused
   i64 live_bytes = 0;
   u64 live_msgs = 0;
   u64 log_used = 0;          // body-log occupancy (head - tail): the oldest live message pins it

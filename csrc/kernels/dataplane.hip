@@ -107,6 +107,7 @@ __global__ __launch_bounds__(1024) void k_stage(DS d) {
       d.tot[TS_HOP_N] = 0;
       d.ctr->spill_moved = 0;
       d.ctr->n_ref = 0; d.ctr->gath_off = 0; d.ctr->ref_bytes = 0;
+      d.ctr->n_maxlen_dropped = 0; d.ctr->n_maxlen_rejected = 0;
       *d.egress_budget = 0;
     }
     // connections whose control command the host has answered resume with this step (the
@@ -1884,6 +1885,7 @@ struct EnqLoad {
   u64 head = 0, tail = 0, mask = 0, ring_off = 0;
   i64 expire_ms = 0, ttl = 0;
   bool durable = false;
+  u32 ql = 0;   // the queue's length limit (q_limit; 0 with DS.limits off)
 };
 DEV EnqLoad enq_load(const DS& d, u32 q, u32 p) {
   const Pub& pb = d.pubs[p];
@@ -1900,13 +1902,24 @@ DEV EnqLoad enq_load(const DS& d, u32 q, u32 p) {
   e.ring_off = d.q_ring_off[q];
   e.ttl = d.q_ttl[q];
   e.durable = d.persist && d.q_durable[q];
+  if (d.limits) e.ql = d.q_limit[q];   // kernel-uniform
   return e;
 }
-DEV u32 enq_store(const DS& d, const EnqLoad& l, u32 q, u32 rank, bool last, PersistRec* pr) {
+// `limited`: the dropped pair was refused by the queue's x-max-length (reject-publish), not by its ring
+DEV u32 enq_store(const DS& d, const EnqLoad& l, u32 q, u32 rank, bool last, PersistRec* pr, bool* limited) {
   const u64 cap = l.mask + 1;
-  const u64 freec = cap - (l.tail - l.head);
+  u64 freec = cap - (l.tail - l.head);
   u32 drop = INVALID;
   if (l.msg == INVALID) return INVALID;
+  if (ql_reject(l.ql)) {
+    // reject-publish: room for L ready entries, the step's earlier pairs of the queue counted by
+    // their rank; requeues may have put the depth above L (room zero, never negative).  The
+    // limit is asked before the ring: where both end at the same pair (a ring of exactly L
+    // slots, or one a requeue filled) the refusal is the limit's
+    const u64 depth = l.tail - l.head, len = ql_len(l.ql);
+    const u64 room = len > depth ? len - depth : 0;
+    if (room <= freec) { freec = room; *limited = true; }
+  }
   if (rank < freec) {
     u64 pos = l.tail + rank;
     Desc ds;
@@ -1930,19 +1943,20 @@ DEV u32 enq_store(const DS& d, const EnqLoad& l, u32 q, u32 rank, bool last, Per
   }
   return drop;
 }
-DEV u32 enqueue_one(const DS& d, u32 src, u32 i, u32 n, PersistRec* pr) {
+DEV u32 enqueue_one(const DS& d, u32 src, u32 i, u32 n, PersistRec* pr, bool* limited) {
   const u32* kk = d.pair_k[src];
   const u32 rb = d.rank_bits;
   u32 q = kk[i] >> rb;
   u32 p = d.pair_v[src][i];
   u32 first = d.q_first[q];   // the queue's first pair (k_qfirst)
-  return enq_store(d, enq_load(d, q, p), q, i - first, (i + 1 == n) || (kk[i + 1] >> rb) != q, pr);
+  return enq_store(d, enq_load(d, q, p), q, i - first, (i + 1 == n) || (kk[i + 1] >> rb) != q, pr, limited);
 }
 // after a pair's enqueue (whole waves: wave collectives): release the message a full ring
-// dropped and count it; record a persistent message's enqueue for the store
-DEV void enqueue_done(const DS& d, u32 drop, const PersistRec& pr) {
+// (or a reject-publish queue at its limit) dropped and count it by the reason; record a
+// persistent message's enqueue for the store
+DEV void enqueue_done(const DS& d, u32 drop, bool limited, const PersistRec& pr) {
   wave_release(d, drop, drop != INVALID);
-  if (drop != INVALID) atomicAdd(&d.ctr->n_ring_full, 1u);
+  if (drop != INVALID) atomicAdd(limited ? &d.ctr->n_maxlen_rejected : &d.ctr->n_ring_full, 1u);
   if (d.persist) {
     const bool want = pr.msg != INVALID;
     const u32 k = wave_reserve(&d.ctr->n_persist, want);
@@ -1977,6 +1991,14 @@ DEV void ring_plan_one(const DS& d, u32 src, u32 i, u32 n) {
 DEV void plan_queue(const DS& d, u32 q, u64 cnt) {
   const u64 head = d.q_head[q], tail = d.q_tail[q];
   d.q_enq_tail[q] = tail;
+  if (d.limits) {   // kernel-uniform: a reject-publish queue takes no more than its room (enq_store)
+    const u32 ql = d.q_limit[q];
+    if (ql_reject(ql)) {
+      const u64 depth = tail - head, len = ql_len(ql);
+      const u64 room = len > depth ? len - depth : 0;
+      if (cnt > room) cnt = room;
+    }
+  }
   const u64 mask = d.q_ring_mask[q], cap = mask + 1;
   const u64 need = tail - head + cnt;
   if (need <= cap) return;
@@ -2037,8 +2059,9 @@ __global__ void k_enqueue(DS d, u32 src) {
     const u32 i = b + threadIdx.x;
     PersistRec pr;
     pr.msg = INVALID;
-    u32 drop = i < n ? enqueue_one(d, src, i, n, &pr) : INVALID;
-    enqueue_done(d, drop, pr);
+    bool limited = false;
+    u32 drop = i < n ? enqueue_one(d, src, i, n, &pr, &limited) : INVALID;
+    enqueue_done(d, drop, limited, pr);
   }
 }
 
@@ -2144,8 +2167,9 @@ __global__ __launch_bounds__(256) void k_rs_scatter_enq(DS d, const u32* kin, co
       PersistRec pr;
       pr.msg = INVALID;
       u32 drop = INVALID;
-      if (valid) drop = enq_store(d, el[c], key[c] >> rb, pos[c] - first[c], pos[c] + 1 == nx[c], &pr);
-      enqueue_done(d, drop, pr);
+      bool limited = false;
+      if (valid) drop = enq_store(d, el[c], key[c] >> rb, pos[c] - first[c], pos[c] + 1 == nx[c], &pr, &limited);
+      enqueue_done(d, drop, limited, pr);
     }
   }
 }
@@ -2485,6 +2509,44 @@ DEV void spill_queue(const DS& d, u32 q, u64 lim, u32 hot, u32 budget, u64* move
 // a consumer's dispatch inputs, loaded by the block's other waves while wave 0 walks the
 // TTL head (thread 0's credit loop then reads them from LDS: only its atomics stay serial)
 struct DqCons { u32 c, ch, ok, noack, pc, glob, unacked; };
+// x-max-length, drop-head (DS.limits; wave 0, on every exit of dequeue_queue that stores q_head,
+// once the step's final head is fixed): the ready entries above the queue's limit leave from
+// the head, oldest first, 64 an iteration like the TTL walk -- after the step's enqueue, requeues,
+// TTL walk, Basic.Gets and dispatch, so a consumer with credit still gets what the step brought
+// and only what would stay queued is bounded.  A trimmed entry goes the way of an expired one
+// (store record kind 1, release); a durable queue on a persisting plane draws on the TTL walk's
+// record budget, and the next steps trim what that did not cover.  The entries of the runs
+// written this step lie below `head` and are not touched.  q_spill_cur and q_cold_lim cope
+// with a head that passes them (spill_queue restarts at the head; k_dequeue, k_cold_scan and
+// k_cold_commit compare them with the head).  Stores q_head[q] if it moved; a dead-letter
+// exchange would take the trimmed entries here.
+DEV void trim_head(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc* ring) {
+  const u32 ql = d.q_limit[q];
+  if (!ql_set(ql) || ql_reject(ql)) return;   // wave-uniform
+  const u64 len = ql_len(ql);
+  if (tail - head <= len) return;
+  const u32 lane = lane_id();
+  const bool budget = d.persist && d.q_durable[q];
+  while (tail - head > len) {
+    if (budget) {
+      u32 ok = 1;
+      if (lane == 0) ok = atomicAdd(&d.tot[TS_TTL_BUDGET], 64u) + 64u <= (d.persist_max >> 2);
+      if (!__shfl(ok, 0, 64)) break;
+    }
+    const u64 over = tail - head - len;
+    const u32 n = over < 64 ? (u32)over : 64u;
+    const u64 idx = head + lane;
+    const bool v = lane < n;
+    Desc ds;
+    ds.msg = INVALID; ds.expire_ms = 0; ds.flags = 0;
+    if (v) ds = ring[idx & mask];
+    wave_consumed(d, ds.msg, q, idx, 1u, v);
+    wave_release(d, ds.msg, v);
+    if (lane == 0) atomicAdd(&d.ctr->n_maxlen_dropped, n);
+    head += n;
+  }
+  if (lane == 0) d.q_head[q] = head;
+}
 DEV bool dequeue_queue(const DS& d) {
   __shared__ u32 g_cons[RUNS_PER_Q];
   __shared__ u32 g_n[RUNS_PER_Q];
@@ -2684,6 +2746,8 @@ DEV bool dequeue_queue(const DS& d) {
   const u64 avail = dlim > head ? dlim - head : 0;
   if (mall == 0 || avail == 0 || nodisp) {
     if (tid == 0) { d.q_head[q] = head; d.q_nruns[q] = ngr; }
+    // (wave 0: thread 0's store of q_head above is ordered before lane 0's in trim_head)
+    if (d.limits && tid < 64) trim_head(d, q, head, tail, mask, ring);
     return true;
   }
   const u32 m = mall > RUNS_PER_Q - ngr ? RUNS_PER_Q - ngr : mall;
@@ -2821,6 +2885,11 @@ DEV bool dequeue_queue(const DS& d) {
     d.q_nruns[q] = nr;
     d.q_head[q] = qp;
     d.q_rr[q] = (r + 1) % mall;
+    if (d.limits) s_head = qp;
+  }
+  if (d.limits) {   // kernel-uniform: the step's final head through LDS to wave 0
+    __syncthreads();
+    if (tid < 64) trim_head(d, q, s_head, tail, mask, ring);
   }
   return true;
 }

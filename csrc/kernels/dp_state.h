@@ -368,4 +368,15 @@ struct DS {
   u32* h_meta;              // [hb_max] pairs | HM_ANY
   u32* h_pair;              // [hb_max] first pair in hp
   u32* hp;                  // [hp_max][HP_WORDS] pair pool
+
+  // ---------------- queue length limits (x-max-length / x-overflow; limits == 0: q_limit is never read)
+  u32 limits;               // kernel-uniform, like persist and links
+  u32* q_limit;             // [q_max] 0: no limit; else (L + 1) | QL_REJECT
 };
+// q_limit: L + 1 in the low bits (so L = 0 differs from "no limit"), the overflow mode on top:
+// drop-head (k_dequeue trims the head down to L at the end of the step) or reject-publish
+// (enq_store refuses the pair that would exceed L)
+enum : u32 { QL_REJECT = 0x80000000u, QL_MAX = 0x7ffffffeu };
+DEV bool ql_set(u32 ql) { return ql != 0; }
+DEV bool ql_reject(u32 ql) { return (ql & QL_REJECT) != 0; }
+DEV u64 ql_len(u32 ql) { return (u64)((ql & ~QL_REJECT) - 1u); }

@@ -189,6 +189,7 @@ class Engine {
     d_.xfer_desc_max = d_.world > 1 ? (u32)get("xfer_desc_max", (d_.world - 1) * d_.pub_max) : 0;
     // persistence + recovery: restore batches reuse the import path (world == 1: own buffers)
     d_.persist = (u32)get("persist", 0);
+    d_.limits = get("queue_limits", 0) ? 1u : 0u;   // x-max-length / x-overflow honoured (q_limit)
     d_.persist_max = d_.persist ? (u32)get("persist_max", d_.cmd_max) : 0;
     d_.persist_bytes = d_.persist ? get("persist_bytes", 64ull << 20) : 0;
     // restore / host-publish records at world 1: recovery batches (persist) and messages
@@ -475,6 +476,7 @@ class Engine {
     d_.ring = (Desc*)dev("ring", sizeof(Desc) * d_.ring_pool);
     d_.ring_top = (u64*)dev("ring_top", 8);
     d_.q_max_cap = (u64*)dev("q_max_cap", 8ull * d_.q_max);
+    d_.q_limit = (u32*)dev("q_limit", 4ull * d_.q_max);
     d_.q_enq_tail = (u64*)dev("q_enq_tail", 8ull * d_.q_max);
     d_.moves = (RingMove*)dev("moves", sizeof(RingMove) * (u64)d_.q_max);
     d_.defer_free = (u32*)dev("defer_free", 4ull * d_.pub_cap);
@@ -961,6 +963,7 @@ class Engine {
     o["h2d_hsa_engine2"] = engine_no(h2d_hsa_, (u32)ing_engine2_);
     o["egress_tail_engine"] = engine_no(copy_mode_ == 3, (u32)tail_engine_);
     o["h2d_split_min"] = h2d_split_min_;
+    o["queue_limits"] = d_.limits;
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
     o["restore_max"] = restore_max_;
     o["xfer_desc_max"] = d_.xfer_desc_max; o["xfer_bytes"] = d_.xfer_bytes; o["world_max"] = WORLD_MAX;
@@ -1555,6 +1558,7 @@ class Engine {
     F(n_acked); F(log_head); F(log_tail); F(msg_free_top); F(n_live_msgs);
     F(n_persist); F(n_consumed); F(persist_used); F(n_persist_overflow);
     F(live_bytes); F(n_grow); F(n_dget); F(spill_moved); F(n_ref); F(gath_off); F(ref_bytes);
+    F(n_maxlen_dropped); F(n_maxlen_rejected);
 #undef F
     std::vector<u32> lat(c.lat_hist, c.lat_hist + LAT_BINS);
     o["lat_hist"] = lat;

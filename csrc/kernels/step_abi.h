@@ -85,6 +85,9 @@ struct Counters {       // per-step counters (device -> host)
   // bytes are egress_bytes - table + ref_bytes
   u32 n_ref, gath_off;
   u64 ref_bytes;
+  // queue length limits (x-max-length; DS.limits): ready entries trimmed from the heads of
+  // drop-head queues, pairs refused by reject-publish queues (neither is in n_expired / n_ring_full)
+  u32 n_maxlen_dropped, n_maxlen_rejected;
 };
 
 struct CtrlRec { u32 conn; u32 off; u32 len; u32 seg; };
