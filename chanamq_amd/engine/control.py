@@ -68,6 +68,11 @@ class Queue:
     # limit); "drop-head" trims the head at the end of a step, "reject-publish" refuses at enqueue
     max_length: Optional[int] = None
     overflow: str = "drop-head"
+    # x-dead-letter-exchange / x-dead-letter-routing-key (dead_letter on): the exchange's name, looked
+    # up in the queue's vhost when a message dies (it need not exist), and the key its dead
+    # letters are published with (None: each message's own)
+    dlx: Optional[str] = None
+    dlk: Optional[bytes] = None
 
 
 @dataclass
@@ -129,7 +134,13 @@ class ControlState:
 
     def __init__(self, c_max=1024, chpc=16, q_max=4096, x_max=1024, cons_max=16384,
                  hash_wildcard=True, ring_pool=1 << 26, default_queue_capacity=1 << 16,
-                 world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False):
+                 world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False, dead_letter=False):
+        # chana.mq.gpu.dead-letter: a queue's x-dead-letter-exchange / x-dead-letter-routing-key are
+        # honoured (off: they are ignored, as the reference does).  Single-rank planes only: the
+        # exchange's queues may live on another rank, which the dead pass cannot reach yet
+        self.dead_letter = bool(dead_letter)
+        if self.dead_letter and world > 1:
+            raise ValueError("dead_letter=True is not served on a sharded plane (world > 1)")
         # chana.mq.gpu.queue-limits: a queue's x-max-length / x-overflow are honoured (off: they
         # are ignored, as the reference does)
         self.queue_limits = bool(queue_limits)
@@ -258,9 +269,22 @@ class ControlState:
             for q in self.queues.values():
                 if q.vhost == vhost:
                     x.bindings.append((q.slot, q.name.encode()))
+        self._dlx_resolve(vhost, name)
         if _sync:
             self.routing_changed()
         return slot
+
+    def _dlx_resolve(self, vhost, name):
+        """Exchange ``name`` appeared or went: the queues that dead-letter to it look it up again."""
+        if self.dead_letter:
+            for q in self.queues.values():
+                if q.dlx == name and q.vhost == vhost:
+                    self.queue_dlx_changed(q)
+
+    def dlx_slot(self, q):
+        """Slot of queue ``q``'s dead-letter exchange as it exists now (None: no such exchange)."""
+        x = self.exchanges.get((q.vhost, q.dlx)) if q.dlx is not None else None
+        return None if x is None else x.slot
 
     def delete_exchange(self, vhost, name, if_unused=False):
         x = self.exchanges.get((vhost, name))
@@ -276,6 +300,7 @@ class ControlState:
             if o.hxbindings:
                 o.hxbindings = [b for b in o.hxbindings if b[0] != x.slot]
         self._free_x.append(x.slot)
+        self._dlx_resolve(vhost, name)
         self.routing_changed()
 
     # ------------------------------------------------------------------ queues
@@ -290,9 +315,14 @@ class ControlState:
         return off
 
     def declare_queue(self, vhost, name, durable=False, exclusive_owner=-1, auto_delete=False,
-                      ttl_ms=0, capacity=None, passive=False, max_capacity=0, max_length=None, overflow="drop-head"):
+                      ttl_ms=0, capacity=None, passive=False, max_capacity=0, max_length=None, overflow="drop-head",
+                      dead_letter_exchange=None, dead_letter_routing_key=None):
         key = (vhost, name)
         q = self.queues.get(key)
+        if not self.dead_letter:
+            dlx = dlk = None
+        else:
+            dlx, dlk = self.check_dead_letter(dead_letter_exchange, dead_letter_routing_key)
         if not self.queue_limits:
             max_length = None
         elif max_length is not None:
@@ -301,6 +331,10 @@ class ControlState:
             # a declare of an existing queue returns its slot; with queue_limits on, a limit that
             # differs from the queue's is refused, but a queue without one (a recovered durable
             # queue: the store keeps no limit) adopts that of the first declare that carries one
+            # (a dead-letter pair that differs is refused first: nothing is changed on a 406)
+            if dlx is not None and not passive and q.dlx is not None and (q.dlx, q.dlk) != (dlx, dlk):
+                raise ControlError(C.PRECONDITION_FAILED, f"queue '{name}' is declared with "
+                                   f"x-dead-letter-exchange '{q.dlx}'", 50, 10)
             if max_length is not None and not passive:
                 if q.max_length is None:
                     q.max_length, q.overflow = max_length, overflow
@@ -308,6 +342,10 @@ class ControlState:
                 elif (q.max_length, q.overflow) != (max_length, overflow):
                     raise ControlError(C.PRECONDITION_FAILED, f"queue '{name}' is declared with x-max-length "
                                        f"{q.max_length} ({q.overflow})", 50, 10)
+            # the dead-letter pair by the same rule (it is not stored either)
+            if dlx is not None and not passive and q.dlx is None:
+                q.dlx, q.dlk = dlx, dlk
+                self.queue_dlx_changed(q)
             return q.slot
         if passive:
             raise ControlError(C.NOT_FOUND, f"no queue '{name}' in vhost '{vhost}'", 50, 10)
@@ -321,7 +359,8 @@ class ControlState:
         slot = self._free_q.pop()
         q = Queue(slot, vhost, name, durable, exclusive_owner, auto_delete, ttl_ms, cap,
                   self._ring_alloc(cap), owner=owner, requested=capacity, max_capacity=max_capacity,
-                  max_length=max_length, overflow=overflow if max_length is not None else "drop-head")
+                  max_length=max_length, overflow=overflow if max_length is not None else "drop-head",
+                  dlx=dlx, dlk=dlk)
         self.queues[key] = q
         self.queue_by_slot[slot] = q
         dx = self.exchanges.get((vhost, ""))
@@ -330,6 +369,24 @@ class ControlState:
         self.queue_declared(q)
         self.routing_changed()
         return slot
+
+    @staticmethod
+    def check_dead_letter(exchange, key):
+        """(exchange name, routing key bytes | None) as a queue keeps them, or 406
+        PRECONDITION_FAILED: both strings of at most 255 bytes, no key without an exchange."""
+        def text(v, what):
+            if isinstance(v, (bytes, bytearray)):
+                v = bytes(v).decode("utf-8", "surrogateescape")
+            if not isinstance(v, str) or len(v.encode("utf-8", "surrogateescape")) > 255:
+                raise ControlError(C.PRECONDITION_FAILED, f"invalid {what} {v!r}", 50, 10)
+            return v
+        if exchange is None:
+            if key is not None:
+                raise ControlError(C.PRECONDITION_FAILED, "x-dead-letter-routing-key without x-dead-letter-exchange",
+                                   50, 10)
+            return None, None
+        return text(exchange, "x-dead-letter-exchange"), \
+            None if key is None else text(key, "x-dead-letter-routing-key").encode("utf-8", "surrogateescape")
 
     OVERFLOW_MODES = ("drop-head", "reject-publish")
     MAX_LENGTH_TOP = 0x7ffffffe   # what the device's q_limit word holds (a larger limit bounds nothing)
@@ -723,4 +780,5 @@ class ControlState:
     def queue_declared(self, q): ...
     def queue_deleted(self, q): ...
     def queue_limit_changed(self, q): ...
+    def queue_dlx_changed(self, q): ...
     def consumers_changed(self, q, cid, removed=False): ...

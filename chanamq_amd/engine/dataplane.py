@@ -21,7 +21,7 @@ from .control import ControlError, ControlState
 from .layout import (CONN_OUT, CONSUMED_REC, EGRESS_REF, RING_MOVE, CTRL_REC, CTRL_DGET, CTRL_TXBUF, INVALID, MF_HAS_TS,
                      MF_HOSTPUB, MF_PERSIST,
                      MF_ONEQ, MF_REDELIVERED, MF_RESTORE,
-                     PERSIST_HDR, RDESC, SEG_IN, SEG_OUT, SS_CTRL, US_ACKED, US_PENDING, US_REQUEUE, USLOT,
+                     PERSIST_HDR, RDESC, SEG_IN, SEG_OUT, SS_CTRL, US_ACKED, US_DEAD, US_PENDING, US_REQUEUE, USLOT,
                      chan_hash, direct_key, exch_hash, fnv1a32, fnv1a64, topic_pattern_row, topic_word_offsets)
 
 ONES64 = np.uint64((1 << 64) - 1)
@@ -72,8 +72,14 @@ class StepResult:
 class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
                  world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
-                 headers_match=False, queue_limits=False, **cfg):
-        """``queue_limits``: queues honour x-max-length / x-overflow (q_limit: trim_head in
+                 headers_match=False, queue_limits=False, dead_letter=False, **cfg):
+        """``dead_letter``: queues honour x-dead-letter-exchange / x-dead-letter-routing-key: entries
+        that expire, are trimmed by x-max-length or are rejected without requeue join the
+        device's dead list and are published to the exchange by the next step's dead pass
+        (k_dead_pack; engine cfg dead_max / dead_bytes bound the list and one pass's payload).
+        Off: the device never reads the fields.  Single-rank planes only.
+
+        ``queue_limits``: queues honour x-max-length / x-overflow (q_limit: trim_head in
         k_dequeue, the refusal in enq_store).  Off: the device never reads the field.
 
         ``headers_match``: headers exchanges match on their bindings' arguments (the
@@ -86,6 +92,8 @@ class GpuDataPlane(ControlState):
         splice it back in; the native front end sends it with sendmsg iovecs).  The caller
         keeps each payload unchanged until the delivering step's egress is collected
         (``step()`` does: a payload buffer is reused two steps later).  None / -1: off."""
+        if dead_letter and world > 1:
+            raise ValueError("dead_letter=True is not served on a sharded plane (world > 1)")
         self.mod = ops.load()
         full = dict(cfg)
         full.setdefault("egress_ref_back", -1 if egress_ref is None else int(egress_ref))
@@ -103,7 +111,8 @@ class GpuDataPlane(ControlState):
             full.setdefault("overlap", 0)
             full.setdefault("copy_engine", 3)
         full.update(device=device, hash_wildcard=int(hash_wildcard), graph=int(graph), world=world, rank=rank,
-                    exchange_lag=int(exchange_lag), queue_limits=int(bool(queue_limits)))
+                    exchange_lag=int(exchange_lag), queue_limits=int(bool(queue_limits)),
+                    dead_letter=int(bool(dead_letter)))
         self.eng = self.mod.Engine(full)
         self.info = self.eng.info()
         sz = self.info["sizeof"]
@@ -158,7 +167,8 @@ class GpuDataPlane(ControlState):
         super().__init__(c_max=i["c_max"], chpc=i["chpc"], q_max=i["q_max"], x_max=i["x_max"],
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
-                         shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits)
+                         shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits,
+                         dead_letter=dead_letter)
 
     # ================================================================== uploads
     # ``defer`` (set by the broker around control work done while steps keep running): table
@@ -415,6 +425,8 @@ class GpuDataPlane(ControlState):
                             ("ch_num", chan.ch, np.uint32), ("ch_unacked", 0, np.uint32),
                             ("ch_win", 0, np.uint32), ("ch_tx", 0, np.uint32)):
             self._up_at(name, v, s, dt)
+        if self.dead_letter:
+            self._up_at("ch_dead_upto", 0, s, np.uint64)
         self._chmap_row(chan.conn)
 
     def channel_changed(self, conn, ch):
@@ -461,6 +473,8 @@ class GpuDataPlane(ControlState):
         self._up_at("q_ttl", q.ttl_ms, q.slot, np.int64)
         if self.queue_limits:
             self.queue_limit_changed(q)
+        if self.dead_letter:
+            self.queue_dlx_changed(q)
         self._up_at("q_rr", 0, q.slot, np.uint32)
         self._up_at("req_q_n", 0, q.slot, np.uint32)
         self._up_at("q_active", 1, q.slot, np.uint32)
@@ -474,8 +488,26 @@ class GpuDataPlane(ControlState):
             ql = (min(int(q.max_length), self.MAX_LENGTH_TOP) + 1) | (0x80000000 if q.overflow == "reject-publish" else 0)
         self._up_at("q_limit", ql, q.slot, np.uint32)
 
+    def queue_dlx_changed(self, q):
+        # q_dlx (dp_state.h): 0 = none; 1 = declared, no such exchange now; else its slot + 2.  The
+        # name and the key, which k_dead_pack writes into the dead letters, go first
+        if q.dlx is None:
+            self._up_at("q_dlx", 0, q.slot, np.uint32)
+            return
+        name = q.dlx.encode("utf-8", "surrogateescape")
+        key = q.dlk or b""
+        row = np.zeros(512, np.uint8)
+        row[:len(name)] = np.frombuffer(name, np.uint8)
+        row[256:256 + len(key)] = np.frombuffer(key, np.uint8)
+        self._write("q_dl_name", row, q.slot * 512)
+        self._up_at("q_dl_len", len(name) | (len(key) << 8) | (0x10000 if q.dlk is not None else 0), q.slot, np.uint32)
+        slot = self.dlx_slot(q)
+        self._up_at("q_dlx", 1 if slot is None else slot + 2, q.slot, np.uint32)
+
     def queue_deleted(self, q):
         self._up_at("q_active", 0, q.slot, np.uint32)
+        if self.dead_letter:   # (a reject of one of its deliveries, still in a window, is then an ack)
+            self._up_at("q_dlx", 0, q.slot, np.uint32)
         if self.defer:
             # a light control section (steps running): no device read.  The host's view of
             # the ring is current up to the ring moves it has seen (FE_GROW); a move still in
@@ -864,10 +896,11 @@ class GpuDataPlane(ControlState):
         s = self.chslot(conn, ch)
         nt = self._u64("ch_next_tag", s)
         requeue = bool(requeue) and kind != "ack"
+        dead = self.dead_letter and kind != "ack" and not requeue   # (US_DEAD / ch_dead_upto: chan_advance_one)
         if tag == 0 and multiple:
             tag = nt - 1
         if multiple:
-            name = "ch_req_upto" if requeue else "ch_ack_upto"
+            name = "ch_req_upto" if requeue else ("ch_dead_upto" if dead else "ch_ack_upto")
             if tag > self._u64(name, s):
                 self._up_at(name, tag, s, np.uint64)
         elif self._u64("ch_uhead", s) <= tag < nt:
@@ -875,7 +908,7 @@ class GpuDataPlane(ControlState):
             off = (s * ucap + ((tag - 1) & (ucap - 1))) * USLOT.itemsize
             st = int(np.frombuffer(self.eng.download("uwin", off, 4), np.uint32)[0])
             if st == US_PENDING:
-                self._up_at("uwin", US_REQUEUE if requeue else US_ACKED, off // 4, np.uint32)
+                self._up_at("uwin", US_REQUEUE if requeue else (US_DEAD if dead else US_ACKED), off // 4, np.uint32)
         self._mark_dirty(s)
 
     def recover(self, conn, ch):

@@ -41,9 +41,16 @@ class _Msg:
 class GoldenDataPlane(ControlState):
     def __init__(self, hash_wildcard=True, ucap=8192, deliver_cap=4096, carry_cap=1 << 20,
                  egress_cap=96 << 20, deliv_max=65536, exchanger=None, xfer_desc_max=1 << 15,
-                 xfer_bytes=1 << 24, persist=False, exchange_lag=0, persist_max=1 << 16, deliver_cap_bytes=0, **kw):
+                 xfer_bytes=1 << 24, persist=False, exchange_lag=0, persist_max=1 << 16, deliver_cap_bytes=0,
+                 dead_max=1024, dead_bytes=8 << 20, restore_max=None, **kw):
         super().__init__(hash_wildcard=hash_wildcard, **kw)
         self.persist = persist
+        # dead-lettering (dead_letter=True): the dead list (the device's: dead_max items) and what
+        # one dead pass takes of it -- min(restore_max, dead_max) records (the import path's
+        # publish slots), dead_bytes of payload in slot layout
+        self.dead, self._dl_row = [], {}
+        self.dead_max, self.dead_bytes = int(dead_max), int(dead_bytes)
+        self.dead_room = min((1 << 14 if persist else 64) if restore_max is None else int(restore_max), self.dead_max)
         # k_dequeue: durable TTL skips <= persist_max / 4 a step; the engine raises
         # persist_max to 2 * deliv_max + 4096 (a step's consumed records always fit)
         self.persist_max = max(persist_max, 2 * deliv_max + 4096) if persist else persist_max
@@ -88,6 +95,7 @@ class GoldenDataPlane(ControlState):
         self._mark_dirty(s)
 
     def queue_declared(self, q):
+        self.queue_dlx_changed(q)
         self.ring[q.slot] = []
         self.qpos_head[q.slot] = 0
         self.qrr[q.slot] = 0
@@ -165,28 +173,120 @@ class GoldenDataPlane(ControlState):
         if c is not None:
             c.paused = False
 
+    SETTLE = ("acked", "requeue", "dead")
+
+    def _settle_kind(self, kind, requeue):
+        """0 ack, 1 requeue, 2 (dead_letter on) a Reject / Nack without requeue: dead-lettered
+        where the queue has a dead-letter exchange, else an ack (off: it is an ack as always)."""
+        if kind == "ack":
+            return 0
+        return 1 if requeue else (2 if self.dead_letter else 0)
+
     def _ack_mark(self, s, tag, multiple, requeue):
         st = self.ch[s]
         if tag == 0 and multiple:
             tag = st["next_tag"] - 1
         if multiple:   # resolved in wire order at the window advance: first cover wins
-            st.setdefault("msettles", []).append((tag, bool(requeue)))
+            st.setdefault("msettles", []).append((tag, int(requeue)))
         elif st["uhead"] <= tag < st["next_tag"]:
             sl = st["slots"].get(tag)
             if sl and sl["state"] == "pending":
-                sl["state"] = "requeue" if requeue else "acked"
+                sl["state"] = self.SETTLE[int(requeue)]
         self._mark_dirty(s)
 
     def apply_ack(self, conn, ch, tag, multiple=False, requeue=False, kind="ack"):
         """Ack / Nack / Reject between steps (Tx.Commit), like GpuDataPlane.apply_ack."""
-        self._ack_mark(self.chslot(conn, ch), tag, multiple, bool(requeue) and kind != "ack")
+        self._ack_mark(self.chslot(conn, ch), tag, multiple, self._settle_kind(kind, requeue))
+
+    # ------------------------------------------------------------------ dead-lettering
+    def _dx(self, q):
+        """Queue slot ``q``'s q_dlx word as the device reads it when an entry dies: None (no
+        dead-letter exchange, or the option off), -1 (declared, no such exchange now), else the
+        exchange's slot."""
+        qq = self.queue_by_slot.get(q) if self.dead_letter else None
+        if qq is None or qq.dlx is None:
+            return None
+        slot = self.dlx_slot(qq)
+        return -1 if slot is None else slot
+
+    def queue_dlx_changed(self, q):
+        # the device's per-slot row of exchange name and key (q_dl_name / q_dl_len): written when a
+        # queue with a pair takes the slot, left as it is otherwise, read by the dead pass
+        if q.dlx is not None:
+            self._dl_row[q.slot] = (q.dlx.encode("utf-8", "surrogateescape"), q.dlk)
+
+    def _dead_join(self, msg, q, qpos, reason, xs, step, ch=0, tag=0):
+        """The entry joins the dead list in place of its release (the list holds the reference).
+        The exchange slot is fixed here; name and key are read from the source slot's row when the
+        pass runs, as k_dead_pack does.  (The holes a chunk of k_chan_advance leaves on the device's
+        list when its record reservation fails after its list reservation are not modelled.)"""
+        self.dead.append(dict(msg=msg, q=q, qpos=qpos, reason=reason, xs=xs, step=max(step, 0), ch=ch, tag=tag))
+        self.counters[("n_dl_expired", "n_dl_maxlen", "n_dl_rejected")[reason]] += 1
+
+    def _dead_leave(self, q, dx, ent, reason, step):
+        """The head entry ``ent`` of queue ``q`` (q_dlx word ``dx``, not None) leaves expired or
+        trimmed (dead_leave in dataplane.hip): a purged entry (expiry 1) is released and never
+        dead-lettered; without the exchange the dead letter is lost; else it joins the list,
+        or -- False -- stays queued because the list is full, which ends the walk."""
+        if ent[2] == 1:
+            self._release(ent[0])
+        elif dx < 0:
+            self.counters["n_dl_unrouted"] += 1
+            self._release(ent[0])
+        elif len(self.dead) >= self.dead_max:
+            return False
+        else:
+            self._dead_join(ent[0], q, self.qpos_head[q], reason, dx, step)
+        return True
+
+    def _dead_pass(self, now_ms):
+        """The dead pass (k_dead_pack + the import path): the pending items in their total order,
+        the longest prefix that fits the pass, each published to its exchange as a new message
+        behind the step's own publishes."""
+        cnt = self.counters
+        items = sorted(self.dead, key=lambda d: (d["step"], d["q"], d["qpos"], d["reason"], d["ch"], d["tag"]))
+        a16 = lambda n: (n + 15) & ~15
+        take = nrec = nbytes = 0
+        for it in items:
+            m = it["msg"]
+            it["ex"], it["rk"] = self._dl_row[it["q"]]
+            rk = m.rk if it["rk"] is None else it["rk"]
+            it["size"] = a16(a16(len(it["ex"]) + len(rk) + len(m.props)) + len(m.body))
+            if it["size"] <= self.dead_bytes:   # (larger than the whole buffer: taken without a record)
+                if nrec >= self.dead_room or nbytes + it["size"] > self.dead_bytes:
+                    break
+                nrec += 1
+                nbytes += it["size"]
+            take += 1
+        taken, self.dead = items[:take], items[take:]
+        for it in taken:
+            m = it["msg"]
+            if it["size"] > self.dead_bytes:
+                cnt["n_dl_dropped"] += 1
+                self._release(m)
+                continue
+            rk = m.rk if it["rk"] is None else it["rk"]
+            x = self.exch_by_slot.get(it["xs"])
+            qs = self._route(x, rk, m.props) if x is not None else []
+            if not qs:
+                cnt["n_dl_unrouted"] += 1
+            else:   # a new message: new id, no channel, never expiring again by its own property
+                new = _Msg(it["ex"], rk, m.props, m.body, len(qs), self.step_no, m.flags & MF_PERSIST, ts=m.ts,
+                           mid=self._mid())
+                self._enqueue(new, qs, 0, now_ms)
+            self._release(m)
 
     def basic_get(self, conn, ch, q, no_ack, now_ms=0):
         """Basic.Get between steps: spec of k_basic_get (dataplane.hip)."""
         ring = self.ring[q]
+        dx = self._dx(q)
         while ring and ring[0][2] and ring[0][2] <= now_ms:
+            if dx is not None and not self._dead_leave(q, dx, ring[0], 0, self.step_no - 1):
+                return None, len(ring)   # the dead list is full: GetEmpty until a step drains it
             self._consumed(ring[0][0], q, self.qpos_head[q], 1)
-            self._release(ring.pop(0)[0])
+            if dx is None:
+                self._release(ring[0][0])
+            ring.pop(0)
             self.qpos_head[q] += 1
         if not ring:
             return None, 0
@@ -537,6 +637,8 @@ class GoldenDataPlane(ControlState):
             if self.lag:   # exchange_lag: import what arrived last step, keep this step's
                 records, self._lag_prev = self._lag_prev, records
             self._import(records, now_ms)
+        if self.dead_letter:   # (world 1) the dead pass, behind the step's own publishes
+            self._dead_pass(now_ms)
         # ---- acks
         for cmd, data in acks:
             o = cmd["m"][0] + 4
@@ -545,7 +647,7 @@ class GoldenDataPlane(ControlState):
             kind = cmd["kind"]
             multiple = bool(bits & 1) if kind != "reject" else False
             requeue = (bits & 1) if kind == "reject" else ((bits >> 1) & 1 if kind == "nack" else 0)
-            self._ack_mark(cmd["chslot"], tag, multiple, requeue)
+            self._ack_mark(cmd["chslot"], tag, multiple, self._settle_kind(kind, requeue))
             cnt["n_acked"] += 1
         # ---- window advance (k_chan_advance)
         dirty, self.dirty = self.dirty, []
@@ -562,9 +664,9 @@ class GoldenDataPlane(ControlState):
                 if up > top:
                     marks.append((up, rq))
                     top = up
-            while t < st["next_tag"]:
-                sl = st["slots"].get(t)
-                state = sl["state"]
+
+            def resolve(t):
+                state = st["slots"][t]["state"]
                 if state == "pending":
                     if t <= st["ack_upto"]:
                         state = "acked"
@@ -573,8 +675,37 @@ class GoldenDataPlane(ControlState):
                     else:
                         for up, rq in marks:
                             if t <= up:
-                                state = "requeue" if rq else "acked"
+                                state = self.SETTLE[rq]
                                 break
+                return state
+
+            deferred = False
+            while t < st["next_tag"]:
+                sl = st["slots"].get(t)
+                if self.dead_letter and not deferred and (t - st["uhead"]) % 256 == 0:
+                    # a 256-tag chunk's rejects join the dead list all or nothing: without room the
+                    # channel keeps its decided marks from here on and stays dirty (chan_advance_one)
+                    need = sum(1 for u in range(t, min(t + 256, st["next_tag"]))
+                               if resolve(u) == "dead" and self._dx(st["slots"][u]["q"]) not in (None, -1))
+                    deferred = need > self.dead_max - len(self.dead)
+                state = resolve(t)
+                if deferred:
+                    sl["state"] = state
+                    contiguous = False
+                    t += 1
+                    continue
+                if state == "dead":
+                    dx = self._dx(sl["q"])
+                    if dx is None or dx < 0:   # no dead-letter exchange (now): an ack
+                        if dx is not None:
+                            cnt["n_dl_unrouted"] += 1
+                        state = "acked"
+                    else:
+                        self._consumed(sl["msg"], sl["q"], sl["qpos"], 0)
+                        self._dead_join(sl["msg"], sl["q"], sl["qpos"], 2, dx, self.step_no, s, t)
+                        self.cons_unacked[sl["cons"]] -= 1
+                        st["unacked"] -= 1
+                        state = "done"
                 if state == "acked":
                     self._consumed(sl["msg"], sl["q"], sl["qpos"], 0)
                     self._release(sl["msg"])
@@ -598,6 +729,8 @@ class GoldenDataPlane(ControlState):
                 st["slots"].pop(k, None)
             st["uhead"] += released
             st["win"] -= released
+            if deferred:
+                self._mark_dirty(s)
         # requeue (k_requeue): back in front of the heads, per queue in queue-position order,
         # before this step's dispatch
         if self.requeue_items:
@@ -669,6 +802,8 @@ class GoldenDataPlane(ControlState):
                 self._consumed(d["msg"], d["q"], d["qpos"], 0)
                 self._release(d["msg"])
         cnt["n_deliv"] = len(delivs)
+        if self.dead_letter:
+            cnt["n_dl_pending"] = len(self.dead)
         self.step_no += 1
         out["counters"] = dict(cnt)
         return out
@@ -834,6 +969,7 @@ class GoldenDataPlane(ControlState):
         # durable queues runs out, and changing it is left to a change of its own
         exact = self.queue_limits and budget_q
         left = 0
+        dx = self._dx(q)   # (dead_letter on, a queue with a dead-letter exchange: the expired join the dead list)
         while ring and (exact or (ring[0][2] and ring[0][2] <= now_ms)):
             if budget_q and not left:   # reserved 64 at a time (dataplane.hip k_dequeue)
                 if self._ttl_budget + 64 > self.persist_max >> 2:
@@ -842,9 +978,13 @@ class GoldenDataPlane(ControlState):
                 left = 64
             if not (ring[0][2] and ring[0][2] <= now_ms):
                 break
+            if dx is not None and not self._dead_leave(q, dx, ring[0], 0, self.step_no):
+                break
             left -= 1
             self._consumed(ring[0][0], q, self.qpos_head[q], 1)
-            self._release(ring.pop(0)[0])
+            if dx is None:
+                self._release(ring[0][0])
+            ring.pop(0)
             self.qpos_head[q] += 1
             cnt["n_expired"] += 1
         # the step's Basic.Gets of this queue, in wire order, ahead of its consumers (spec of
@@ -932,14 +1072,19 @@ class GoldenDataPlane(ControlState):
         if not self.queue_limits or qq.max_length is None or qq.overflow != "drop-head":
             return
         budget_q = self.persist and qq.durable
+        dx = self._dx(q)
         while len(ring) > qq.max_length:
             if budget_q:
                 if self._ttl_budget + 64 > self.persist_max >> 2:
                     break
                 self._ttl_budget += 64
             for _ in range(min(64, len(ring) - qq.max_length)):
+                if dx is not None and not self._dead_leave(q, dx, ring[0], 1, self.step_no):
+                    return   # the dead list is full: the next steps go on
                 self._consumed(ring[0][0], q, self.qpos_head[q], 1)
-                self._release(ring.pop(0)[0])
+                if dx is None:
+                    self._release(ring[0][0])
+                ring.pop(0)
                 self.qpos_head[q] += 1
                 self.counters["n_maxlen_dropped"] += 1
 

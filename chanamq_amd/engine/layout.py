@@ -31,6 +31,7 @@ assert PERSIST_HDR.itemsize == 48 and CONSUMED_REC.itemsize == 32
 USLOT = np.dtype([("state", "<u4"), ("msg", "<u4"), ("q", "<u4"), ("cons", "<u4"), ("qpos", "<u8"),
                   ("expire_ms", "<i8")])
 US_FREE, US_PENDING, US_ACKED, US_REQUEUE, US_DONE = 0, 1, 2, 3, 4
+US_DEAD = 5   # (dead_letter on) rejected / nacked without requeue
 CTRL_TXBUF = 0x80000000     # CtrlRec.seg: data command of a transactional channel (low bits = position)
 CTRL_DGET = 0x40000000      # CtrlRec.seg: a Basic.Get its step decoded but could not serve (not paused)
 

@@ -219,7 +219,8 @@ class GpuBroker:
                  ingress_bytes=64 << 20, per_conn_read=256 << 10, mem_high_watermark=None, mem_low_watermark=None,
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
-                 persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False):
+                 persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False,
+                 dead_letter=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -241,6 +242,14 @@ class GpuBroker:
         self.queue_limits = bool(queue_limits)
         if self.queue_limits and not getattr(plane, "queue_limits", False):
             raise ValueError("queue_limits=True needs a data plane built with queue_limits=True")
+        # dead-lettering (chana.mq.gpu.dead-letter): Queue.Declare's x-dead-letter-exchange /
+        # x-dead-letter-routing-key are parsed and passed to the plane (built with dead_letter=True,
+        # which serves them); off, they are ignored as always before.  Single node only
+        self.dead_letter = bool(dead_letter)
+        if self.dead_letter and not getattr(plane, "dead_letter", False):
+            raise ValueError("dead_letter=True needs a data plane built with dead_letter=True")
+        if self.dead_letter and node is not None:
+            raise ValueError("dead_letter=True is not served on a sharded node")
         native_x = bool(getattr(plane, "native_xchg", False))
         if io == "auto":
             io = "pipeline" if (hasattr(plane, "eng") and (node is None or native_x)) else "native"
@@ -351,6 +360,8 @@ class GpuBroker:
         self.stats = dict(steps=0, published=0, delivered=0, connections=0)
         if self.queue_limits:
             self.stats.update(maxlen_dropped=0, maxlen_rejected=0)
+        if self.dead_letter:
+            self.stats.update(dict.fromkeys(self.DL_STATS, 0))
         self.lock = _PlaneLock(self)
         self.light = _LightLock(self.lock)
 
@@ -812,6 +823,8 @@ class GpuBroker:
         self.stats.update(steps=st["steps"], published=st["published"], delivered=st["delivered"])
         if self.queue_limits:
             self.stats.update(maxlen_dropped=st.get("maxlen_dropped", 0), maxlen_rejected=st.get("maxlen_rejected", 0))
+        if self.dead_letter:
+            self.stats.update({k: st.get(k, 0) for k in self.DL_STATS})
         if st.get("spill_moved"):
             self.stats["spilled_bytes"] = st["spill_moved"]
         self._fe_stats = st
@@ -1237,6 +1250,10 @@ class GpuBroker:
         if self.queue_limits:   # x-max-length: trimmed from drop-head queues / refused by reject-publish queues
             self.stats["maxlen_dropped"] += cnt.get("n_maxlen_dropped", 0)
             self.stats["maxlen_rejected"] += cnt.get("n_maxlen_rejected", 0)
+        if self.dead_letter:   # dead-lettered by reason, dead letters lost, entries pending on the device's list
+            for k in self.DL_STATS[:-1]:
+                self.stats[k] += cnt.get("n_" + k, 0)
+            self.stats["dl_pending"] = cnt.get("n_dl_pending", 0)
         for conn, code, chslot in events:
             c = self.conns.get(conn)
             if c is None or c.state != "open":
@@ -1496,6 +1513,28 @@ class GpuBroker:
         expire_ms = now + int(exp) if isinstance(exp, str) and exp.isdigit() else 0
         return now, flags, expire_ms, ts_ms
 
+    DL_STATS = ("dl_expired", "dl_maxlen", "dl_rejected", "dl_unrouted", "dl_dropped", "dl_pending")
+
+    def _dlx_args(self, m):
+        """Queue.Declare's x-dead-letter-exchange / x-dead-letter-routing-key as ``declare_queue``
+        keywords, with dead-letter on ({} with it off: the arguments are ignored as always
+        before).  A value that is no string of at most 255 bytes, or the key without the
+        exchange, is 406 PRECONDITION_FAILED with nothing changed (``check_dead_letter``); a pair
+        that differs from the existing queue's is refused by ``declare_queue``."""
+        if not self.dead_letter:
+            return {}
+        args = m.arguments or {}
+
+        def val(name):
+            v = args.get(name)
+            if isinstance(v, Typed):
+                v = v.value if v.tag == "S" else v   # (any other type: refused below)
+            return bytes(v).decode("utf-8", "surrogateescape") if isinstance(v, (bytes, bytearray)) else v
+        ex, key = self.plane.check_dead_letter(val("x-dead-letter-exchange"), val("x-dead-letter-routing-key"))
+        if ex is None:
+            return {}
+        return dict(dead_letter_exchange=ex, dead_letter_routing_key=key)
+
     def _limit_args(self, m, q=None):
         """Queue.Declare's x-max-length / x-overflow as ``declare_queue`` keywords, with
         queue-limits on ({} with it off, or without a limit: the arguments are ignored as always
@@ -1650,7 +1689,8 @@ class GpuBroker:
             if q is not None and q.exclusive_owner not in (-1, c.id):
                 raise ControlError(C.RESOURCE_LOCKED, f"queue '{name}' is exclusive to another connection", 50, 10)
             slot = p.declare_queue(vh, name, durable=m.durable, exclusive_owner=c.id if m.exclusive else -1,
-                                   auto_delete=m.auto_delete, ttl_ms=ttl, passive=m.passive, **self._limit_args(m))
+                                   auto_delete=m.auto_delete, ttl_ms=ttl, passive=m.passive, **self._limit_args(m),
+                                   **self._dlx_args(m))
             c.last_queue[ch] = name
             if self.persistence is not None and q is None and not m.passive:
                 self.persistence.queue(p.queue_by_slot[slot])
@@ -1824,7 +1864,8 @@ class GpuBroker:
             if q is None:   # client-local placement: the queue lives on the declaring rank
                 node.submit("place_queue", vh, name, p.rank)
             seq = node.submit("declare_queue", vh, name, durable=m.durable, auto_delete=m.auto_delete,
-                              ttl_ms=int(args.get("x-message-ttl", 0) or 0), **lim)
+                              ttl_ms=int(args.get("x-message-ttl", 0) or 0), **lim,
+                              **self._dlx_args(m))   # ({} here: dead-letter is refused on a sharded node)
             c.last_queue[ch] = name
 
             def reply(r, name=name):

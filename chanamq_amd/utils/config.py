@@ -292,6 +292,10 @@ class Config:
         queue_limits = bool(g(k + "queue-limits", False))
         if queue_limits:
             plane.update(queue_limits=True)
+        # queues honour Queue.Declare's x-dead-letter-exchange / x-dead-letter-routing-key (off: ignored)
+        dead_letter = bool(g(k + "dead-letter", False))
+        if dead_letter:
+            plane.update(dead_letter=True, dead_max=int(g(k + "dead-max", 1024)), dead_bytes=int(g(k + "dead-bytes", 8 << 20)))
         hi = int(g("chana.mq.flow.memory-high-watermark", -1))
         lo = int(g("chana.mq.flow.memory-low-watermark", -1))
         if hi < 0:   # 40% of what the broker can hold: the HBM body log + the host spill ring
@@ -303,7 +307,7 @@ class Config:
                       confirm_read=int(g(k + "confirm-read", 128 << 10)),
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
-                      headers_match=headers_match, queue_limits=queue_limits,
+                      headers_match=headers_match, queue_limits=queue_limits, dead_letter=dead_letter,
                       mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 

@@ -323,6 +323,8 @@ PYBIND11_MODULE(_core, m) {
              o["dropped_nomem"] = s.dropped_nomem; o["ring_full"] = s.ring_full; o["unroutable"] = s.unroutable;
              o["routed"] = s.routed; o["expired"] = s.expired; o["ctrl"] = s.ctrl; o["log_used"] = s.log_used;
              o["maxlen_dropped"] = s.maxlen_dropped; o["maxlen_rejected"] = s.maxlen_rejected;
+             o["dl_expired"] = s.dl_expired; o["dl_maxlen"] = s.dl_maxlen; o["dl_rejected"] = s.dl_rejected;
+             o["dl_unrouted"] = s.dl_unrouted; o["dl_dropped"] = s.dl_dropped; o["dl_pending"] = s.dl_pending;
              o["wait_s"] = s.wait_s;
              o["submit_s"] = s.submit_s;
              o["xchg_s"] = s.xchg_s; o["xchg_steps"] = s.xchg_steps; o["syncs"] = s.syncs;

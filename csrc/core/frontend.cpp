@@ -1302,6 +1302,12 @@ void Frontend::finish_oldest(std::deque<Inflight>& inflight) {
     stats_.expired += c.n_expired;
     stats_.maxlen_dropped += c.n_maxlen_dropped;
     stats_.maxlen_rejected += c.n_maxlen_rejected;
+    stats_.dl_expired += c.n_dl_expired;
+    stats_.dl_maxlen += c.n_dl_maxlen;
+    stats_.dl_rejected += c.n_dl_rejected;
+    stats_.dl_unrouted += c.n_dl_unrouted;
+    stats_.dl_dropped += c.n_dl_dropped;
+    stats_.dl_pending = c.n_dl_pending;
     stats_.ctrl += c.n_ctrl;
     stats_.live_msgs = c.n_live_msgs;
     stats_.log_used = c.log_head - c.log_tail;

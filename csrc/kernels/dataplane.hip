@@ -313,6 +313,7 @@ DEV u32 build_keyvec_win(const DS& d, const Win32& s, u32 n, u32 pi) {
 // grows, so k_chan_advance resolves the step's multiple settles in wire order (ack index
 // = command order): a tag's fate is the first settle covering it, e.g. Nack(4, requeue)
 // then Ack(8) requeues 1-4.  Marks only depend on earlier steps' deliveries.
+template <bool DLX>   // DS.dlx as a compile-time constant: the flag-off kernel holds none of the dead-letter code
 DEV void apply_ack(const DS& d, Ack a, u32 ai) {
   const u32 ch = a.chslot;
   if (ch == INVALID) { d.acks[ai] = a; return; }
@@ -322,12 +323,15 @@ DEV void apply_ack(const DS& d, Ack a, u32 ai) {
   a.tag = tag;
   d.acks[ai] = a;
   const bool requeue = (a.kind != CK_ACK) && a.requeue;
+  // DS.dlx: a Reject / Nack without requeue is its own mark (dead-lettered where the queue has
+  // a dead-letter exchange, else an ack: chan_advance_one); off, it is an ack as always
+  const bool dead = DLX && (a.kind != CK_ACK) && !a.requeue;
   if (a.multiple) {
     atomicMin(&d.ch_mlo[ch], ai);
     atomicMax(&d.ch_mhi[ch], ai);
   } else if (tag >= d.ch_uhead[ch] && tag < nt) {
     USlot& u = d.uwin[(u64)ch * (d.ucap_mask + 1) + ((tag - 1) & d.ucap_mask)];
-    atomicCAS(&u.state, (u32)US_PENDING, requeue ? (u32)US_REQUEUE : (u32)US_ACKED);
+    atomicCAS(&u.state, (u32)US_PENDING, requeue ? (u32)US_REQUEUE : (dead ? (u32)US_DEAD : (u32)US_ACKED));
   }
   if (atomicExch(&d.ch_dirty[ch], 1u) == 0) {
     u32 k = atomicAdd(d.n_dirty, 1u);
@@ -556,13 +560,14 @@ __global__ __launch_bounds__(256) void k_decode(DS d) {
 // k_render (engine overlap).  Also the routing half's per-step resets.
 // (fused into k_route_store, phase 0: the marks only have to precede k_chan_advance, and
 // the snowflake id floor moved into log_reserve, its one reader -- a launch less per step)
+template <bool DLX>
 DEV void marks_range(const DS& d, u32 i0, u32 stride) {
   if (i0 == 0 && d.links)
     for (u32 r = 0; r < WORLD_MAX; ++r) d.lk_cnt[r] = 0;
   const u32 na = d.ctr->n_acks, np = d.ctr->n_pubs;
   const u32 n = na > np ? na : np;
   for (u32 i = i0; i < n; i += stride) {
-    if (i < na) apply_ack(d, d.acks[i], i);
+    if (i < na) apply_ack<DLX>(d, d.acks[i], i);
     if (i < np) {
       const u32 ch = d.pubs[i].chslot;
       if (ch != INVALID && d.ch_confirm[ch]) atomicAdd(&d.ch_pub_cnt[ch], 1u);
@@ -1490,11 +1495,12 @@ DEV void write_slot(u8* dst, const u8* w, const Pub& pb, const Frag* frags) {
 // fill its MsgEnt and copy exchange / rk / props / body into the log (fused k_route<1> +
 // k_store: one pass over the phase's publishes)
 DEV void store_one_pre(const DS& d, u32 p, u32 lane, const Pub& pb, u32 nq, u32 rr, u32 soff, u32 wbase);
+template <bool DLX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_route_store(DS d, u32 marks) {
   u32 lane = lane_id();
   if (blockIdx.x == 0 && threadIdx.x < 64) live_add_blocks(d, lane);
   // phase 0 (the step's own commands): K9 ack marks + K10 confirm counts (fused k_marks)
-  if (marks) marks_range(d, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  if (marks) marks_range<DLX>(d, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
   u32 n = d.tot[TS_RANGE_HI];
   if (n > d.pub_cap) n = d.pub_cap;
   const u32 nw = (gridDim.x * blockDim.x) >> 6;
@@ -1866,6 +1872,164 @@ DEV void import_one(const DS& d, u32 i, const u32* xr) {
   d.pubs[pi] = pb;
 }
 
+// ============================================================================ dead pass (DS.dlx)
+// The entries on the dead list become publishes to their queues' dead-letter exchanges, in
+// the step after the one they died in: k_dead_pack renders them as import records (RDesc +
+// [exchange name][routing key][props][body] in slot layout) into the dead-letter buffers, and
+// k_import_route / k_scan_route / k_route_store, given a DS view whose receive side is those
+// buffers, route and store them behind the step's own publishes -- the order phase B of a
+// sharded step uses -- for the step's one sort and enqueue.
+//
+// Phase 0, one 1024-thread block: the pending items ordered by (step died, queue slot, queue
+// position, reason, channel slot, tag) -- a total order, whatever order the blocks of
+// k_dequeue and k_chan_advance appended them in -- by counting ranks over the keys in LDS
+// (32 KB; each thread compares its key with every other, an LDS broadcast per read); the
+// longest prefix that fits the pass's records (`room`) and payload (dead_bytes) is taken, the
+// rest moves to the list's front.  An item whose record is larger than the whole payload
+// buffer, or whose body went to the cold store, is taken without a record (n_dl_dropped); a
+// hole (msg INVALID) is taken silently.  Phase 1, one wave per taken item: its record and
+// payload, then the list's reference is dropped.  Phase 2, after the pass's routing: the records
+// that reached no queue are counted (n_dl_unrouted).
+DEV bool dead_key_less(const u64* a, const u64* b) {
+  if (a[0] != b[0]) return a[0] < b[0];
+  if (a[1] != b[1]) return a[1] < b[1];
+  if (a[2] != b[2]) return a[2] < b[2];
+  return a[3] < b[3];
+}
+// record bytes of item `it` in slot layout (0: a hole); *lens = exchange name | key << 8 bytes
+DEV u32 dead_rec_size(const DS& d, const DeadItem& it, u32* lens, bool* cold) {
+  *lens = 0;
+  *cold = false;
+  if (it.msg == INVALID) return 0;
+  const MsgEnt& m = d.msgs[it.msg];
+  const u32 ql = d.dl->q_dl_len[it.q];
+  const u32 exl = ql & 255u, rkl = (ql & DLQ_HAS_KEY) ? ((ql >> 8) & 255u) : (u32)m.rk_len;
+  *lens = exl | (rkl << 8);
+  *cold = (m.log_off & COLD_BIT) != 0;
+  return align16(align16(exl + rkl + m.props_len) + m.body_len);
+}
+__global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
+  const u32 tid = threadIdx.x, lane = lane_id();
+  if (phase == 0) {
+    __shared__ u64 key[DEAD_LIST_MAX][4];
+    __shared__ u32 perm[DEAD_LIST_MAX];
+    __shared__ u32 lds[1024 / 64 + 1];
+    __shared__ u32 s_take;
+    if (blockIdx.x) return;
+    u32 n = d.dl->dead_n[0];
+    if (n > d.dl->dead_max) n = d.dl->dead_max;
+    if (n == 0) {   // block-uniform: nothing pending, the pass imports nothing
+      if (tid == 0) {
+        d.dl->dead_n[1] = 0;
+        d.dl->dead_xchg[XC_RECV_N] = d.dl->dead_xchg[XC_RECV_B] = d.dl->dead_xchg[XC_RECV_AN] = d.dl->dead_xchg[XC_RECV_AB] = 0;
+      }
+      return;
+    }
+    if (tid < n) {
+      const DeadItem it = d.dl->dead[tid];
+      key[tid][0] = ((u64)it.step << 32) | it.q;
+      key[tid][1] = it.qpos;
+      key[tid][2] = ((u64)it.reason << 32) | it.ch;
+      key[tid][3] = it.tag;
+    }
+    if (tid == 0) s_take = n;
+    __syncthreads();
+    if (tid < n) {
+      u32 r = 0;
+      for (u32 j = 0; j < n; ++j) r += (dead_key_less(key[j], key[tid]) || (j < tid && !dead_key_less(key[tid], key[j]))) ? 1u : 0u;
+      perm[r] = tid;
+    }
+    __syncthreads();
+    // thread t: the item at ordered position t (read before anything is written back)
+    DeadItem it;
+    it.msg = INVALID; it.q = 0; it.qpos = 0; it.step = 0; it.reason = 0; it.ch = 0; it.xs = 0; it.tag = 0;
+    u32 sz = 0, lens = 0;
+    bool cold = false;
+    if (tid < n) {
+      it = d.dl->dead[perm[tid]];
+      sz = dead_rec_size(d, it, &lens, &cold);
+    }
+    const bool hole = tid < n && it.msg == INVALID;
+    const bool drop = tid < n && !hole && (cold || (u64)sz > d.dl->dead_bytes);
+    const bool rec = tid < n && !hole && !drop;
+    u32 tot_b, tot_r;
+    const u32 off = block_scan<1024>(rec ? sz : 0u, lds, tot_b);
+    const u32 ri = block_scan<1024>(rec ? 1u : 0u, lds, tot_r);
+    // (offsets grow with the position: the first item that does not fit ends the prefix)
+    if (rec && (ri >= room || (u64)off + sz > d.dl->dead_bytes)) atomicMin(&s_take, tid);
+    __syncthreads();
+    const u32 take = s_take;
+    if (tid < take) {
+      d.dl->dead_take[tid] = it;
+      d.dl->dead_off[2 * tid] = rec ? ri : INVALID;
+      d.dl->dead_off[2 * tid + 1] = off;
+      if (drop) atomicAdd(&d.ctr->n_dl_dropped, 1u);
+    } else if (tid < n) {
+      d.dl->dead[tid - take] = it;
+    }
+    if (tid == (take ? take - 1 : 0u)) {   // the pass's totals: those of the last taken item
+      const u32 nr = take ? ri + (rec ? 1u : 0u) : 0u, nb = take ? off + (rec ? sz : 0u) : 0u;
+      d.dl->dead_n[0] = n - take;
+      d.dl->dead_n[1] = take;
+      d.dl->dead_xchg[XC_RECV_N] = d.dl->dead_xchg[XC_RECV_AN] = nr;
+      d.dl->dead_xchg[XC_RECV_B] = d.dl->dead_xchg[XC_RECV_AB] = nb;
+    }
+    return;
+  }
+  if (phase == 2) {
+    // behind the pass's routing: a dead letter its exchange routed to no queue is lost, and counted
+    // (here, not in route_one: the routing kernels are the ones every publish of every step runs)
+    u32 hi = d.tot[TS_RANGE_HI];
+    if (hi > d.pub_cap) hi = d.pub_cap;
+    const u32 gs = gridDim.x * blockDim.x;
+    for (u32 p0 = d.tot[TS_RANGE_LO] + blockIdx.x * blockDim.x; p0 < hi; p0 += gs) {   // (wave-uniform trips)
+      const u32 p = p0 + tid;
+      const u64 m = __ballot(p < hi && d.pub_nq[p] == 0);
+      if (lane == 0 && m) atomicAdd(&d.ctr->n_dl_unrouted, (u32)__popcll(m));
+    }
+    return;
+  }
+  // phase 1: one wave per taken item
+  const u32 take = d.dl->dead_n[1] < d.dl->dead_max ? d.dl->dead_n[1] : d.dl->dead_max;
+  const u32 nw = (gridDim.x * blockDim.x) >> 6;
+  for (u32 t = (blockIdx.x * blockDim.x + tid) >> 6; t < take; t += nw) {
+    const DeadItem it = d.dl->dead_take[t];
+    const u32 ri = d.dl->dead_off[2 * t], off = d.dl->dead_off[2 * t + 1];
+    if (ri != INVALID && it.msg != INVALID) {
+      const MsgEnt m = d.msgs[it.msg];
+      const u32 ql = d.dl->q_dl_len[it.q];
+      const u32 exl = ql & 255u;
+      const bool own = !(ql & DLQ_HAS_KEY);
+      const u32 rkl = own ? (u32)m.rk_len : ((ql >> 8) & 255u);
+      const u8* slot = msg_slot(d, m.log_off);
+      const u8* names = d.dl->q_dl_name + (u64)it.q * (2 * DLQ_STR);
+      u8* dst = d.dl->dead_pay + off;
+      wave_copy(dst, names, exl);
+      wave_copy(dst + exl, own ? slot + m.ex_len : names + DLQ_STR, rkl);
+      wave_copy(dst + exl + rkl, slot + m.ex_len + m.rk_len, m.props_len);
+      wave_copy(dst + align16(exl + rkl + m.props_len), slot + m.body_off, m.body_len);
+      if (lane == 0) {
+        RDesc rd{};
+        rd.pay_off = off;
+        rd.body_len = m.body_len;
+        rd.props_len = m.props_len;
+        rd.exch = (i32)it.xs;
+        // a new message without a publisher: never mandatory or immediate, never expiring again
+        // by its own property (the target queue's x-message-ttl still applies at its enqueue)
+        rd.flags = (m.flags & (MF_PERSIST | MF_HAS_TS)) | MF_SLOTFMT;
+        rd.ex_len = (u8)exl;
+        rd.rk_len = (u8)rkl;
+        rd.expire_ms = 0;
+        rd.ts_ms = m.ts_ms;
+        rd.pad[0] = it.q;        // (source queue and reason: for x-death, later)
+        rd.pad[1] = it.reason;
+        d.dl->dead_desc[ri] = rd;
+      }
+    }
+    wave_release(d, it.msg, lane == 0);   // the list's reference (a hole: nothing)
+  }
+}
+
 // ============================================================================ K7 enqueue
 __global__ void k_qfirst(DS d, u32 src) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2212,6 +2376,57 @@ DEV void wave_consumed(const DS& d, u32 msg, u32 q, u64 qpos, u32 kind, bool val
   if (want && k < d.persist_max) consumed_rec_at(d, msg, q, qpos, kind, k);
 }
 
+// ---- dead-lettering (DS.dlx): the dead list.  k_dequeue's walks reserve what they can get
+// (reserve_upto: exact, one wave per queue contends); k_chan_advance reserves a 256-tag chunk's
+// rejects all or nothing.  The count never passes dead_max and granted ranges never overlap.
+// k_dead_pack, the only reader, runs in the next step, behind every writer on the routing stream
+DEV u32 dead_reserve_all(const DS& d, u32 n) {
+  u32 cur = __hip_atomic_load(&d.dl->dead_n[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (true) {
+    if (cur + n > d.dl->dead_max) return INVALID;
+    const u32 prev = atomicCAS(&d.dl->dead_n[0], cur, cur + n);
+    if (prev == cur) return cur;
+    cur = prev;
+  }
+}
+DEV void dead_put(const DS& d, u32 k, u32 step, u32 msg, u32 q, u64 qpos, u32 reason, u32 xs, u32 ch, u64 tag) {
+  // (field by field: a 40-byte store would hold ten registers at once in k_chan_advance)
+  volatile DeadItem* it = d.dl->dead + k;
+  it->msg = msg; it->q = q; it->qpos = qpos; it->step = step; it->reason = reason;
+  it->ch = ch; it->xs = xs; it->tag = tag;
+}
+// One wave, at the head of queue q whose q_dlx word is dx (not 0): the wave's first n lanes hold
+// entries (msg at position idx, ring expiry exp) that leave the queue expired or trimmed.
+// Purged entries (expiry 1, Queue.Purge's mark) are released and never dead-lettered; the
+// others join the dead list in place of their release, as far as it has room.  Returns how
+// many of the n entries left (all of them, or those before the first the list had no room
+// for: the walk stops there and the next steps go on); the caller writes their consumed
+// records and moves the head
+DEV u32 dead_leave(const DS& d, u32 dx, u32 step, u32 msg, i64 exp, u32 q, u64 idx, u32 reason, u32 n) {
+  const u32 lane = lane_id();
+  const bool dead = lane < n && exp != 1 && msg != INVALID;
+  const u64 dm = __ballot(dead);
+  const u32 want = (u32)__popcll(dm);
+  if (dx == 1u) {   // the exchange does not exist (now): lost, like a publish to no queue
+    wave_release(d, msg, lane < n);
+    if (lane == 0 && want) atomicAdd(&d.ctr->n_dl_unrouted, want);
+    return n;
+  }
+  u32 g = 0, b = 0;
+  if (lane == 0 && want) g = reserve_upto(&d.dl->dead_n[0], want, d.dl->dead_max, &b);
+  g = (u32)__shfl((int)g, 0, 64);
+  b = (u32)__shfl((int)b, 0, 64);
+  const u32 rank = (u32)__popcll(dm & lanemask_lt());
+  if (dead && rank < g) dead_put(d, b + rank, step, msg, q, idx, reason, dx - 2u, 0u, 0ull);
+  if (g < want) {   // the lane of the first entry without room: nothing from it on leaves
+    const u64 first = __ballot(dead && rank == g);
+    n = (u32)__ffsll((unsigned long long)first) - 1u;
+  }
+  wave_release(d, msg, lane < n && !dead);
+  if (lane == 0 && g) atomicAdd(reason == DL_EXPIRED ? &d.ctr->n_dl_expired : &d.ctr->n_dl_maxlen, g);
+  return n;
+}
+
 
 // ============================================================================ K9 window advance
 // one block (4 waves) per dirty channel: resolve marks, release/requeue, advance the
@@ -2223,25 +2438,31 @@ struct MsLds {
   u32 wc[4];
   u32 rc[4];     // store records per wave of the current chunk
   u32 rbase;     // their block reservation (INVALID: budget exhausted)
+  u32 dc[4];     // (DS.dlx) dead-list items per wave of the current chunk
+  u32 dbase;     // their block reservation (INVALID: the list is full)
   u32 n, nb;
-  unsigned long long ovf_a, ovf_r;
+  unsigned long long ovf_a, ovf_r, ovf_d;
 };
+template <bool DLX>
 DEV void chan_advance_one(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, u32* s_first, u32* s_done, MsLds& ms);
+template <bool DLX>
 __global__ __launch_bounds__(256) void k_chan_advance(DS d) {
   __shared__ u32 s_first[4];
   __shared__ u32 s_done[4];
   __shared__ MsLds ms;
   const u32 tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const u32 nd = *d.n_dirty;
-  for (u32 wv = blockIdx.x; wv < nd; wv += gridDim.x) chan_advance_one(d, d.dirty_list[wv], tid, lane, w, s_first,
+  for (u32 wv = blockIdx.x; wv < nd; wv += gridDim.x) chan_advance_one<DLX>(d, d.dirty_list[wv], tid, lane, w, s_first,
                                                                         s_done, ms);
 }
 
 // the channel's multiple settles of this step (ack indices [lo, hi]) in wire order, reduced
 // to record-breaking uptos: ms.up[0..nb) increasing, the first one >= t decides tag t
+// (ms.rq: 0 ack, 1 requeue, 2 -- DS.dlx only -- rejected without requeue)
+template <bool DLX>
 DEV void collect_settles(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, MsLds& ms) {
   const u32 lo = d.ch_mlo[ch], hi = d.ch_mhi[ch];
-  if (tid == 0) { ms.n = 0; ms.nb = 0; ms.ovf_a = 0; ms.ovf_r = 0; }
+  if (tid == 0) { ms.n = 0; ms.nb = 0; ms.ovf_a = 0; ms.ovf_r = 0; ms.ovf_d = 0; }
   __syncthreads();
   if (lo == INVALID) return;   // block-uniform
   for (u32 base = lo; base <= hi; base += 256) {
@@ -2253,7 +2474,7 @@ DEV void collect_settles(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, MsLds& m
       a = d.acks[i];
       take = a.chslot == ch && a.multiple;
     }
-    const bool rq = (a.kind != CK_ACK) && a.requeue;
+    const u32 rq = a.kind != CK_ACK ? (a.requeue ? 1u : (DLX ? 2u : 0u)) : 0u;
     const u64 m = __ballot(take);
     if (lane == 0) ms.wc[w] = (u32)__popcll(m);
     __syncthreads();
@@ -2261,7 +2482,7 @@ DEV void collect_settles(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, MsLds& m
     for (u32 k = 0; k < w; ++k) pos += ms.wc[k];
     if (take) {
       if (pos < MS_MAX) { ms.up[pos] = a.tag; ms.rq[pos] = rq; }
-      else atomicMax(rq ? &ms.ovf_r : &ms.ovf_a, (unsigned long long)a.tag);
+      else atomicMax(rq == 1u ? &ms.ovf_r : ((DLX && rq) ? &ms.ovf_d : &ms.ovf_a), (unsigned long long)a.tag);
     }
     __syncthreads();
     if (tid == 0) ms.n += ms.wc[0] + ms.wc[1] + ms.wc[2] + ms.wc[3];
@@ -2273,9 +2494,10 @@ DEV void collect_settles(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, MsLds& m
     u32 nb = 0;
     for (u32 k = 0; k < n; ++k)
       if (ms.up[k] > top) { ms.up[nb] = ms.up[k]; ms.rq[nb] = ms.rq[k]; ++nb; top = ms.up[k]; }
-    const u64 oa = ms.ovf_a, orq = ms.ovf_r;   // past MS_MAX: the larger cover, appended
-    const u64 om = oa > orq ? oa : orq;
-    if (om > top) { ms.up[nb] = om; ms.rq[nb] = orq > oa; ++nb; }
+    // past MS_MAX: the largest cover with its kind, appended (equal covers: ack, then requeue)
+    const u64 oa = ms.ovf_a, orq = ms.ovf_r, od = DLX ? ms.ovf_d : 0ull;
+    const u64 om = oa > orq ? (oa > od ? oa : od) : (orq > od ? orq : od);
+    if (om > top) { ms.up[nb] = om; ms.rq[nb] = oa == om ? 0u : (orq == om ? 1u : 2u); ++nb; }
     ms.nb = nb;
     d.ch_mlo[ch] = INVALID;
     d.ch_mhi[ch] = 0;
@@ -2298,11 +2520,13 @@ DEV u32 ca_reserve(const DS& d, u32 n) {
   }
 }
 
+template <bool DLX>
 DEV void chan_advance_one(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, u32* s_first, u32* s_done, MsLds& ms) {
-  collect_settles(d, ch, tid, lane, w, ms);
+  collect_settles<DLX>(d, ch, tid, lane, w, ms);
   const u32 nb = ms.nb;
   const u64 head = d.ch_uhead[ch], nt = d.ch_next_tag[ch];
   const u64 aup = d.ch_ack_upto[ch], rup = d.ch_req_upto[ch];
+  const u64 dup = DLX ? d.dl->ch_dead_upto[ch] : 0ull;
   USlot* win = d.uwin + (u64)ch * (d.ucap_mask + 1);
   bool contiguous = true;
   bool deferred = false;   // block-uniform: the record budget ran out at some chunk
@@ -2320,19 +2544,40 @@ DEV void chan_advance_one(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, u32* s_
       if (st == US_PENDING) {   // host marks (between steps) first, then this step's settles
         if (t <= aup) st = US_ACKED;
         else if (t <= rup) st = US_REQUEUE;
+        else if (DLX && t <= dup) st = US_DEAD;
         else
           for (u32 k = 0; k < nb; ++k)
-            if (t <= ms.up[k]) { st = ms.rq[k] ? US_REQUEUE : US_ACKED; break; }
+            if (t <= ms.up[k]) { st = ms.rq[k] == 1u ? US_REQUEUE : ((DLX && ms.rq[k]) ? US_DEAD : US_ACKED); break; }
       }
     }
-    const bool acked = valid && st == US_ACKED;
+    bool acked = valid && st == US_ACKED;
     const bool req = valid && st == US_REQUEUE;
+    // DS.dlx: a rejected entry whose queue has a dead-letter exchange joins the dead list in
+    // place of its release (its record is the ack's); on any other queue it is an ack
+    bool dead = false, unrouted = false;
+    if (DLX) {
+      if (valid && st == US_DEAD) {
+        const u32 dxs = u.q < d.q_max ? d.dl->q_dlx[u.q] : 0u;
+        dead = dxs >= 2u;
+        unrouted = dxs == 1u;
+        acked = !dead;
+      }
+      const u64 dmk = __ballot(dead);
+      if (lane == 0) ms.dc[w] = (u32)__popcll(dmk);
+      __syncthreads();
+      if (tid == 0) {
+        const u32 tot = ms.dc[0] + ms.dc[1] + ms.dc[2] + ms.dc[3];
+        ms.dbase = deferred ? INVALID : (tot ? dead_reserve_all(d, tot) : 0u);
+      }
+      __syncthreads();
+      if (ms.dbase == INVALID) deferred = true;   // the list is full: the marks stay, like past the record budget
+    }
     // store records of this chunk, reserved for the whole block within the step's budget.
     // Past the budget the channel keeps its decided marks (ACKED / REQUEUE slot states,
     // which the next step resolves first) and stays dirty (a burst of settles
     // of durable persistent messages must not overflow persist_max and stop the broker)
     u32 rec_k = INVALID;
-    const bool want_rec = wants_record(d, u.msg, u.q, acked || req);
+    const bool want_rec = wants_record(d, u.msg, u.q, acked || req || dead);
     if (d.persist) {   // kernel-uniform
       const u64 rm = __ballot(want_rec);
       if (lane == 0) ms.rc[w] = (u32)__popcll(rm);
@@ -2342,16 +2587,33 @@ DEV void chan_advance_one(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, u32* s_
         ms.rbase = deferred ? INVALID : (tot ? ca_reserve(d, tot) : 0u);
       }
       __syncthreads();
-      if (ms.rbase == INVALID) deferred = true;
+      if (ms.rbase == INVALID && !deferred) {
+        deferred = true;
+        if (DLX) {   // the chunk's dead-list reservation stays behind as holes (k_dead_pack skips them)
+          const u64 dmk = __ballot(dead);
+          u32 k = ms.dbase + (u32)__popcll(dmk & lanemask_lt());
+          for (u32 j = 0; j < w; ++j) k += ms.dc[j];
+          if (dead) dead_put(d, k, (u32)d.in->step, INVALID, u.q, u.qpos, DL_REJECTED, 0u, ch, t);
+        }
+      }
       if (!deferred) {
         rec_k = ms.rbase + (u32)__popcll(rm & lanemask_lt());
         for (u32 k = 0; k < w; ++k) rec_k += ms.rc[k];
       }
     }
     if (deferred) {   // block-uniform
-      if (valid && (st == US_ACKED || st == US_REQUEUE) && st != u.state) win[(t - 1) & d.ucap_mask].state = st;
+      if (valid && (st == US_ACKED || st == US_REQUEUE || st == US_DEAD) && st != u.state) win[(t - 1) & d.ucap_mask].state = st;
       contiguous = false;
       continue;
+    }
+    if (DLX) {
+      const u64 dmk = __ballot(dead);
+      u32 k = ms.dbase + (u32)__popcll(dmk & lanemask_lt());
+      for (u32 j = 0; j < w; ++j) k += ms.dc[j];
+      if (dead) dead_put(d, k, (u32)d.in->step, u.msg, u.q, u.qpos, DL_REJECTED, d.dl->q_dlx[u.q] - 2u, ch, t);
+      const u32 nun = (u32)__popcll(__ballot(unrouted));
+      if (lane == 0 && dmk) atomicAdd(&d.ctr->n_dl_rejected, (u32)__popcll(dmk));
+      if (lane == 0 && nun) atomicAdd(&d.ctr->n_dl_unrouted, nun);
     }
     // requeue list (one reservation per wave)
     u32 rtot;
@@ -2363,13 +2625,13 @@ DEV void chan_advance_one(const DS& d, u32 ch, u32 tid, u32 lane, u32 w, u32* s_
       d.req[ri] = r;
     }
     wave_add_u32(d.req_q_n, u.q, 1u, req_ok);
-    link_consumed(d, u.msg, u.q, acked ? 0u : (req_ok ? 4u : 2u), acked || req);
-    if (want_rec) consumed_rec_at(d, u.msg, u.q, u.qpos, acked ? 0u : (req_ok ? 4u : 2u), rec_k);
+    link_consumed(d, u.msg, u.q, (acked || dead) ? 0u : (req_ok ? 4u : 2u), acked || req || dead);
+    if (want_rec) consumed_rec_at(d, u.msg, u.q, u.qpos, (acked || dead) ? 0u : (req_ok ? 4u : 2u), rec_k);
     wave_release(d, u.msg, acked || (req && !req_ok));
-    wave_sub_u32(d.cons_unacked, u.cons, 1u, acked || req);
-    manual_done += __popcll(__ballot(acked || req));
+    wave_sub_u32(d.cons_unacked, u.cons, 1u, acked || req || dead);
+    manual_done += __popcll(__ballot(acked || req || dead));
     if (lane == 0 && rtot) atomicAdd(&d.ctr->n_requeue, rtot);
-    if (acked || req) st = US_DONE;
+    if (acked || req || dead) st = US_DONE;
     if (valid && st != u.state) win[(t - 1) & d.ucap_mask].state = st;
     if (contiguous) {   // block-uniform
       // both ballots wave-wide (a ballot inside the lane-0 branch would see one lane)
@@ -2520,6 +2782,7 @@ struct DqCons { u32 c, ch, ok, noack, pc, glob, unacked; };
 // with a head that passes them (spill_queue restarts at the head; k_dequeue, k_cold_scan and
 // k_cold_commit compare them with the head).  Stores q_head[q] if it moved; a dead-letter
 // exchange would take the trimmed entries here.
+template <bool DLX>
 DEV void trim_head(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc* ring) {
   const u32 ql = d.q_limit[q];
   if (!ql_set(ql) || ql_reject(ql)) return;   // wave-uniform
@@ -2527,26 +2790,39 @@ DEV void trim_head(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc*
   if (tail - head <= len) return;
   const u32 lane = lane_id();
   const bool budget = d.persist && d.q_durable[q];
-  while (tail - head > len) {
+  // DS.dlx, a queue with a dead-letter exchange: as in the TTL walk, the trimmed entries join
+  // the dead list as far as it has room, and the trim ends where bodies may be cold
+  const u32 dx = DLX ? d.dl->q_dlx[q] : 0u;   // wave-uniform
+  const u64 clim = dx ? d.q_cold_lim[q] : ~0ull;
+  while (tail - head > len && head < clim) {
     if (budget) {
       u32 ok = 1;
       if (lane == 0) ok = atomicAdd(&d.tot[TS_TTL_BUDGET], 64u) + 64u <= (d.persist_max >> 2);
       if (!__shfl(ok, 0, 64)) break;
     }
-    const u64 over = tail - head - len;
-    const u32 n = over < 64 ? (u32)over : 64u;
+    u64 over = tail - head - len;
+    if (over > clim - head) over = clim - head;
+    u32 n = over < 64 ? (u32)over : 64u;
     const u64 idx = head + lane;
-    const bool v = lane < n;
     Desc ds;
     ds.msg = INVALID; ds.expire_ms = 0; ds.flags = 0;
-    if (v) ds = ring[idx & mask];
+    if (lane < n) ds = ring[idx & mask];
+    bool full = false;
+    if (dx) {
+      const u32 left = dead_leave(d, dx, (u32)d.in->step, ds.msg, ds.expire_ms, q, idx, DL_MAXLEN, n);
+      full = left < n;
+      n = left;
+    }
+    const bool v = lane < n;
     wave_consumed(d, ds.msg, q, idx, 1u, v);
-    wave_release(d, ds.msg, v);
-    if (lane == 0) atomicAdd(&d.ctr->n_maxlen_dropped, n);
+    if (!dx) wave_release(d, ds.msg, v);
+    if (lane == 0 && n) atomicAdd(&d.ctr->n_maxlen_dropped, n);
     head += n;
+    if (full) break;
   }
   if (lane == 0) d.q_head[q] = head;
 }
+template <bool DLX>
 DEV bool dequeue_queue(const DS& d) {
   __shared__ u32 g_cons[RUNS_PER_Q];
   __shared__ u32 g_n[RUNS_PER_Q];
@@ -2624,25 +2900,37 @@ DEV bool dequeue_queue(const DS& d) {
     // quarter of the step's record buffer (reserved 64 at a time) and the next steps
     // continue it -- the record buffer never overflows (the store would miss deletions)
     const bool budget = d.persist && d.q_durable[q];
-    while (head < tail) {
+    // DS.dlx, a queue with a dead-letter exchange: the expired entries join the dead list
+    // (dead_leave) as far as it has room, and the walk ends at the first position whose body
+    // may be cold (k_dead_pack could not copy it; k_cold_scan pages the head window back in)
+    const u32 dx = DLX ? d.dl->q_dlx[q] : 0u;   // wave-uniform
+    u64 wend = tail;
+    if (dx && d.q_cold_lim[q] < wend) wend = d.q_cold_lim[q];
+    while (head < wend) {
       if (budget) {
         u32 ok = 1;
         if (lane == 0) ok = atomicAdd(&d.tot[TS_TTL_BUDGET], 64u) + 64u <= (d.persist_max >> 2);
         if (!__shfl(ok, 0, 64)) break;
       }
       u64 idx = head + lane;
-      bool valid = idx < tail;
+      bool valid = idx < wend;
       Desc ds;
       ds.msg = INVALID; ds.expire_ms = 0; ds.flags = 0;
       if (valid) ds = ring[idx & mask];
       bool exp = valid && ds.expire_ms != 0 && ds.expire_ms <= now;
       u64 live = __ballot(valid && !exp);
       u32 nexp = live ? (__ffsll((unsigned long long)live) - 1) : __popcll(__ballot(valid));
+      bool full = false;
+      if (dx) {
+        const u32 left = dead_leave(d, dx, (u32)d.in->step, ds.msg, ds.expire_ms, q, idx, DL_EXPIRED, nexp);
+        full = left < nexp;
+        nexp = left;
+      }
       wave_consumed(d, ds.msg, q, idx, 1u, lane < nexp);
-      wave_release(d, ds.msg, lane < nexp);
+      if (!dx) wave_release(d, ds.msg, lane < nexp);
       if (lane == 0 && nexp) atomicAdd(&d.ctr->n_expired, nexp);
       head += nexp;
-      if (live) break;
+      if (live || full) break;
     }
     if (lane == 0) { s_head = head; s_bytes = 0; }
   } else if (!nodisp && tid - 64 < RUNS_PER_Q) {   // the consumers' inputs, beside the TTL walk
@@ -2747,7 +3035,7 @@ DEV bool dequeue_queue(const DS& d) {
   if (mall == 0 || avail == 0 || nodisp) {
     if (tid == 0) { d.q_head[q] = head; d.q_nruns[q] = ngr; }
     // (wave 0: thread 0's store of q_head above is ordered before lane 0's in trim_head)
-    if (d.limits && tid < 64) trim_head(d, q, head, tail, mask, ring);
+    if (d.limits && tid < 64) trim_head<DLX>(d, q, head, tail, mask, ring);
     return true;
   }
   const u32 m = mall > RUNS_PER_Q - ngr ? RUNS_PER_Q - ngr : mall;
@@ -2889,7 +3177,7 @@ DEV bool dequeue_queue(const DS& d) {
   }
   if (d.limits) {   // kernel-uniform: the step's final head through LDS to wave 0
     __syncthreads();
-    if (tid < 64) trim_head(d, q, s_head, tail, mask, ring);
+    if (tid < 64) trim_head<DLX>(d, q, s_head, tail, mask, ring);
   }
   return true;
 }
@@ -2898,11 +3186,12 @@ DEV bool dequeue_queue(const DS& d) {
 // step's delivery runs (runs_body, once the kernel k_runs: a launch less per step)
 template <u32 NT> DEV void runs_body(const DS& d, u64* key_lds, u32 key_cap, u32* lds);
 #define DQ_RUN_LDS 2048   // runs that runs_body sorts in LDS (more: the global-memory sort)
+template <bool DLX>
 __global__ __launch_bounds__(256) void k_dequeue(DS d) {
   __shared__ u64 key_lds[DQ_RUN_LDS];
   __shared__ u32 lds[256 / 64 + 1];
   __shared__ u32 s_last;
-  const bool wrote = dequeue_queue(d);
+  const bool wrote = dequeue_queue<DLX>(d);
   // every block's runs and counts reach the device-wide coherence point before its ticket
   // (agent scope: the last block may run on another XCD, whose L2 does not see this one's);
   // a block that wrote no runs stored its zero count agent-coherent and skips the L2
@@ -3600,6 +3889,7 @@ DEV void final_step(const DS& d) {
   c->n_live_msgs = d.msg_max - *d.msg_free_top;
   c->live_bytes = *d.live_bytes;
   c->n_dget = d.tot[TS_NDGET];
+  if (d.dlx) c->n_dl_pending = d.dl->dead_n[0] < d.dl->dead_max ? d.dl->dead_n[0] : d.dl->dead_max;
   if (d.links)
     for (u32 r = 0; r < d.world; ++r) d.xchg[XC_ACK_N + r] = d.lk_cnt[r] < d.lk_cap ? d.lk_cnt[r] : d.lk_cap;
   *d.ctr_host = *c;
@@ -3726,14 +4016,18 @@ DEV void host_out_copies(const DS& d, u64 gtid, u64 gsz) {
 // no-ack: a done slot, the message is released now.  GetOk + content header + body frames
 // (split at the connection's frame-max) are rendered into `out` (host-mapped).
 // Consumer bookkeeping uses the spare consumer slot cons_max.
+// DS.dlx, a queue with a dead-letter exchange: the expired entries join the dead list, stamped
+// with `step` (the last step submitted), and the next step's dead pass takes them; where the
+// list has no room the answer is GetEmpty (the entries behind wait for a step to drain it)
 __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack, i64 now, u8* out, u64 out_cap,
-                                                  GetRes* res) {
+                                                  GetRes* res, u32 step) {
   u32 lane = lane_id();
   u64 head = d.q_head[q], tail = d.q_tail[q];
   const u64 mask = d.q_ring_mask[q];
   const Desc* ring = d.ring + d.q_ring_off[q];
   u32 nexp = 0;
-  bool more_expired = false;
+  bool more_expired = false, full = false;
+  const u32 dx = d.dlx ? d.dl->q_dlx[q] : 0u;
   if (head < tail) {
     u64 idx = head + lane;
     bool valid = idx < tail;
@@ -3744,6 +4038,11 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
     u64 live = __ballot(valid && !exp);
     nexp = live ? (__ffsll((unsigned long long)live) - 1) : __popcll(__ballot(valid));
     more_expired = !live && head + nexp < tail;
+    if (dx) {
+      const u32 left = dead_leave(d, dx, step, ds.msg, ds.expire_ms, q, idx, DL_EXPIRED, nexp);
+      full = left < nexp;
+      nexp = left;
+    }
     bool mine = lane < nexp;
     bool rec = mine && d.q_durable[q] && (d.msgs[ds.msg].flags & MF_PERSIST);
     u64 rm = __ballot(rec);
@@ -3756,16 +4055,16 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
       r.pad[0] = r.pad[1] = 0;
       res->exp[__popcll(rm & lanemask_lt())] = r;
     }
-    wave_release(d, ds.msg, mine);
+    if (!dx) wave_release(d, ds.msg, mine);
     if (lane == 0) res->n_exp = __popcll(rm);
     head += nexp;
   } else if (lane == 0) {
     res->n_exp = 0;
   }
-  if (head >= tail || more_expired) {
+  if (head >= tail || more_expired || full) {
     if (lane == 0) {
       d.q_head[q] = head;
-      res->status = more_expired ? GET_RETRY : GET_EMPTY;
+      res->status = (more_expired && !full) ? GET_RETRY : GET_EMPTY;
       res->msg_count = (u32)(tail - head);
       res->out_len = 0;
     }

@@ -56,7 +56,11 @@ enum : u32 {
 };
 
 // ---- unacked slot states
-enum : u32 { US_FREE = 0, US_PENDING = 1, US_ACKED = 2, US_REQUEUE = 3, US_DONE = 4 };
+enum : u32 {
+  US_FREE = 0, US_PENDING = 1, US_ACKED = 2, US_REQUEUE = 3, US_DONE = 4,
+  US_DEAD = 5   // (DS.dlx) rejected / nacked without requeue: dead-lettered if its queue has a
+                // dead-letter exchange when the window advance gets to it, else an ack
+};
 
 
 // StepIn.ref_back flag: only bodies in the host spill ring go by reference this step
@@ -245,6 +249,23 @@ struct USlot {          // per-channel unacked window slot
 };
 
 struct ReqItem { u32 q; u32 msg; u64 qpos; i64 expire_ms; };
+
+// dead-lettering (DS.dlx): an entry that left queue q dead -- expired at the head, trimmed by
+// x-max-length, or rejected without requeue -- while q had a dead-letter exchange.  The list
+// holds the message's reference until k_dead_pack has rendered it as a publish to exchange
+// slot xs (the slot q_dlx named when the entry died).  msg == INVALID: a hole (a reservation
+// k_chan_advance could not use), skipped by the pack
+enum : u32 { DL_EXPIRED = 0, DL_MAXLEN = 1, DL_REJECTED = 2 };
+struct DeadItem {
+  u32 msg, q;
+  u64 qpos;
+  u32 step;             // (u32)StepIn.step of the step it died in
+  u32 reason;           // DL_*
+  u32 ch;               // DL_REJECTED: channel slot and delivery tag (else 0)
+  u32 xs;
+  u64 tag;
+};
+static_assert(sizeof(DeadItem) == 40, "DeadItem layout");
 
 // Basic.Get result (k_basic_get -> host-mapped); exp[] = persistent messages of durable
 // queues dropped by the TTL skip (their store rows go, like ConsumedRec kind 1)

@@ -85,6 +85,7 @@ enum : u32 {
                       // shipped to links), no TTL skip on live link shadows
 };
 
+struct DlState;
 struct DS {
   // ---------------- sizes
   u32 c_max, chpc, q_max, x_max, cons_max, seg_max;
@@ -372,7 +373,29 @@ struct DS {
   // ---------------- queue length limits (x-max-length / x-overflow; limits == 0: q_limit is never read)
   u32 limits;               // kernel-uniform, like persist and links
   u32* q_limit;             // [q_max] 0: no limit; else (L + 1) | QL_REJECT
+
+  // ---------------- dead-lettering (x-dead-letter-exchange / -routing-key; dlx == 0: dl is never read)
+  u32 dlx;                  // kernel-uniform, like limits: 1 on; 2 in the DS view of the dead pass
+  const DlState* dl;        // device: the feature's tables and buffers (one pointer here: DS is the argument
+                            // of every kernel of every step, the flag on or off)
 };
+struct DlState {
+  u32 dead_max;             // items of the dead list (<= DEAD_LIST_MAX)
+  u64 dead_bytes;           // payload bytes of one dead pass
+  u32* q_dlx;               // [q_max] 0: none; 1: declared, no such exchange now; else its slot + 2
+  u32* q_dl_len;            // [q_max] name bytes | key bytes << 8 | DLQ_HAS_KEY
+  u8* q_dl_name;            // [q_max][2 * DLQ_STR] exchange name, then x-dead-letter-routing-key
+  u64* ch_dead_upto;        // [chslots] host mark (Tx.Commit): tags up to it are rejected without requeue
+  DeadItem* dead;           // [dead_max] the dead list, in arrival order
+  u32* dead_n;              // [0] items on the list; [1] items this step's dead pass took
+  DeadItem* dead_take;      // [dead_max] those items, ordered (k_dead_pack phase 0 -> 1)
+  u32* dead_off;            // [dead_max][2] their record index and payload offset (INVALID: no record)
+  RDesc* dead_desc;         // [dead_max] the dead pass's records (DS.recv_desc of its view)
+  u8* dead_pay;             // [dead_bytes] and payload (DS.recv_pay)
+  u32* dead_xchg;           // [XC_WORDS] and receive counts (DS.xchg), written by k_dead_pack
+};
+#define DEAD_LIST_MAX 1024  // k_dead_pack orders the list in one 1024-thread block
+enum : u32 { DLQ_STR = 256, DLQ_HAS_KEY = 0x10000u };
 // q_limit: L + 1 in the low bits (so L = 0 differs from "no limit"), the overflow mode on top:
 // drop-head (k_dequeue trims the head down to L at the end of the step) or reject-publish
 // (enq_store refuses the pair that would exceed L)

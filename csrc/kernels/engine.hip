@@ -200,6 +200,28 @@ class Engine {
       d_.pub_cap = ((d_.pub_max + d_.import_max + 63) / 64) * 64;
     }
     d_.pair_max = (u32)get("pair_max", d_.cmd_max * 4);
+    // dead-lettering (x-dead-letter-exchange honoured): the dead list and the dead pass's own
+    // import buffers.  The pass's records run through the import path of a world-1 engine
+    // (publish slots and fragments past the step's own: pub_cap, frag_max + i), so it takes
+    // at most import_max of them a step
+    d_.dlx = get("dead_letter", 0) ? 1u : 0u;
+    if (d_.dlx) {
+      if (d_.world != 1)
+        throw std::runtime_error("dead_letter: single-rank planes only (a dead-letter exchange's queues may live on "
+                                 "another rank, which needs the cross-rank pack path)");
+      dl_h_.dead_max = (u32)get("dead_max", 1024);
+      dl_h_.dead_bytes = get("dead_bytes", 8ull << 20);
+      if (dl_h_.dead_max < 1 || dl_h_.dead_max > DEAD_LIST_MAX)
+        throw std::runtime_error("dead_max must be 1.." + std::to_string(DEAD_LIST_MAX) + " (k_dead_pack orders the list in one block)");
+      if (dl_h_.dead_bytes < 16 || dl_h_.dead_bytes + 8192 > (4ull << 30))
+        throw std::runtime_error("dead_bytes must be 16 B .. 4 GiB (u32 offsets)");
+      if (!d_.import_max)
+        throw std::runtime_error("dead_letter needs the import path's publish slots: restore_max must not be 0");
+      dead_room_ = std::min(d_.import_max, dl_h_.dead_max);
+      // every record of the pass is at least one pair behind the step's own publishes' pairs
+      if ((u64)d_.pair_max < (u64)d_.pub_max + dead_room_)
+        throw std::runtime_error("dead_letter: pair_max must cover a step's publishes plus the dead pass (pub_max + min(restore_max, dead_max))");
+    }
     d_.deliv_max = (u32)get("deliv_max", 65536);
     if (d_.persist) {
       // a step's consumed-store records: deliveries (<= deliv_max), the durable TTL skip
@@ -256,7 +278,7 @@ class Engine {
       // a step's persist records: one 48-B header per enqueue (<= pair_max) and each
       // message's bytes once (<= the step's work buffer + what it imported), so the
       // packed buffer can never overflow (no fail-closed stop on a burst)
-      const u64 need = d_.work_cap + d_.xfer_bytes + 56ull * d_.pair_max + 4096;
+      const u64 need = d_.work_cap + d_.xfer_bytes + dl_h_.dead_bytes + 56ull * d_.pair_max + 4096;   // (+ the dead pass's messages)
       if (d_.persist_bytes < need) d_.persist_bytes = need;
       if (d_.persist_max < d_.pair_max) d_.persist_max = d_.pair_max;
     }
@@ -477,6 +499,22 @@ class Engine {
     d_.ring_top = (u64*)dev("ring_top", 8);
     d_.q_max_cap = (u64*)dev("q_max_cap", 8ull * d_.q_max);
     d_.q_limit = (u32*)dev("q_limit", 4ull * d_.q_max);
+    if (d_.dlx) {
+      dl_h_.q_dlx = (u32*)dev("q_dlx", 4ull * d_.q_max);
+      dl_h_.q_dl_len = (u32*)dev("q_dl_len", 4ull * d_.q_max);
+      dl_h_.q_dl_name = (u8*)dev("q_dl_name", 2ull * DLQ_STR * d_.q_max);
+      dl_h_.ch_dead_upto = (u64*)dev("ch_dead_upto", 8ull * d_.c_max * d_.chpc);
+      dl_h_.dead = (DeadItem*)dev("dead", sizeof(DeadItem) * (u64)dl_h_.dead_max);
+      dl_h_.dead_n = (u32*)dev("dead_n", 16);
+      dl_h_.dead_take = (DeadItem*)dev("dead_take", sizeof(DeadItem) * (u64)dl_h_.dead_max);
+      dl_h_.dead_off = (u32*)dev("dead_off", 8ull * dl_h_.dead_max);
+      dl_h_.dead_desc = (RDesc*)dev("dead_desc", sizeof(RDesc) * (u64)dl_h_.dead_max);
+      dl_h_.dead_pay = (u8*)dev("dead_pay", dl_h_.dead_bytes + 64);
+      dl_h_.dead_xchg = (u32*)dev("dead_xchg", 4ull * XC_WORDS);
+      DlState* dl = (DlState*)dev("dl_state", sizeof(DlState));
+      HIPCHECK(hipMemcpy(dl, &dl_h_, sizeof(DlState), hipMemcpyHostToDevice));
+      d_.dl = dl;
+    }
     d_.q_enq_tail = (u64*)dev("q_enq_tail", 8ull * d_.q_max);
     d_.moves = (RingMove*)dev("moves", sizeof(RingMove) * (u64)d_.q_max);
     d_.defer_free = (u32*)dev("defer_free", 4ull * d_.pub_cap);
@@ -964,6 +1002,7 @@ class Engine {
     o["egress_tail_engine"] = engine_no(copy_mode_ == 3, (u32)tail_engine_);
     o["h2d_split_min"] = h2d_split_min_;
     o["queue_limits"] = d_.limits;
+    o["dead_letter"] = d_.dlx; o["dead_max"] = dl_h_.dead_max; o["dead_bytes"] = dl_h_.dead_bytes; o["dead_room"] = dead_room_;
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
     o["restore_max"] = restore_max_;
     o["xfer_desc_max"] = d_.xfer_desc_max; o["xfer_bytes"] = d_.xfer_bytes; o["world_max"] = WORLD_MAX;
@@ -988,6 +1027,8 @@ class Engine {
   int npar_ = 2;           // per-step IO sets in use (of NPAR_MAX)
   bool lag_ = false, native_x_ = false, links_ = false;
   u32 restore_max_ = 0;
+  u32 dead_room_ = 0;      // records one dead pass takes: min(import_max, dead_max)
+  DlState dl_h_{};         // host copy of DS.dl
   u64 carry_budget_ = 0;
   int copy_mode_ = 0;      // cfg copy_engine
   bool sdma_ = true;       // copy_engine 1: NoCU copy requests
@@ -1559,6 +1600,9 @@ class Engine {
     F(n_persist); F(n_consumed); F(persist_used); F(n_persist_overflow);
     F(live_bytes); F(n_grow); F(n_dget); F(spill_moved); F(n_ref); F(gath_off); F(ref_bytes);
     F(n_maxlen_dropped); F(n_maxlen_rejected);
+    // (only with dead_letter on: off, a step's counters are the dict they were -- each entry is a
+    // string and a hash on the host's per-step path, which the headline benchmark drives)
+    if (d_.dlx) { F(n_dl_expired); F(n_dl_maxlen); F(n_dl_rejected); F(n_dl_unrouted); F(n_dl_dropped); F(n_dl_pending); }
 #undef F
     std::vector<u32> lat(c.lat_hist, c.lat_hist + LAT_BINS);
     o["lat_hist"] = lat;
@@ -2495,7 +2539,7 @@ class Engine {
     Range rg("chanamq.basic_get");
     sync();
     hipLaunchKernelGGL(k_basic_get, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms, get_out_dev_,
-                       get_cap_, get_res_dev_);
+                       get_cap_, get_res_dev_, (u32)(seq_ ? seq_ - 1 : 0));   // (the last step submitted; before the first: 0)
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s_comp_));
     const GetRes& r = *get_res_h_;
@@ -2695,7 +2739,10 @@ class Engine {
                                  &d.tot[TS_RANGE_HI], d.pub_cap, TS_ROUTE, &d.tot[TS_RANGE_LO]);
     hipLaunchKernelGGL(k_scan_route, dim3(ceil_div(d.pub_cap ? d.pub_cap : 1, SCAN_TILE)), dim3(1024), 0, s, a, d.tot,
                        scan_status_, scan_ctl_, scan_smax_, d);
-    hipLaunchKernelGGL(k_route_store, wave_blocks(nmax), dim3(256), 0, s, d, imports ? 0u : 1u);
+    // (the kernels that hold dead-letter code exist twice: with the flag off the step runs the
+    // instantiation without any of it)
+    if (d.dlx) hipLaunchKernelGGL(k_route_store<true>, wave_blocks(nmax), dim3(256), 0, s, d, imports ? 0u : 1u);
+    else hipLaunchKernelGGL(k_route_store<false>, wave_blocks(nmax), dim3(256), 0, s, d, imports ? 0u : 1u);
   }
 
   // serialise publishes with remote owners into the per-destination send buffers
@@ -2742,10 +2789,12 @@ class Engine {
       if (!fin) hipLaunchKernelGGL(k_host_out, dim3(64), dim3(256), 0, s, d);
       return;
     }
-    hipLaunchKernelGGL(k_chan_advance, capped(nch, 1024), dim3(256), 0, s, d);
+    if (d.dlx) hipLaunchKernelGGL(k_chan_advance<true>, capped(nch, 1024), dim3(256), 0, s, d);
+    else hipLaunchKernelGGL(k_chan_advance<false>, capped(nch, 1024), dim3(256), 0, s, d);
     // k_dequeue first puts requeued deliveries back in front of their queues' heads, in
     // queue-offset order (QueueEntity.scala:415-446), then dispatches
-    hipLaunchKernelGGL(k_dequeue, dim3(d.q_max), dim3(256), 0, s, d);   // (its last block lays out the runs)
+    if (d.dlx) hipLaunchKernelGGL(k_dequeue<true>, dim3(d.q_max), dim3(256), 0, s, d);
+    else hipLaunchKernelGGL(k_dequeue<false>, dim3(d.q_max), dim3(256), 0, s, d);   // (its last block lays out the runs)
     hipLaunchKernelGGL(k_dv_write, blocks(d.deliv_max, 256), dim3(256), 0, s, d);
     if (d.c_max <= CONN_LAYOUT_MAX) {
       hipLaunchKernelGGL(k_conn_layout, dim3(1), dim3(1024), 0, s, d);   // + the delivery-size scan
@@ -2770,12 +2819,39 @@ class Engine {
     }
   }
 
+  // dead-lettering (DS.dlx, world 1): the entries that died in earlier steps, rendered as
+  // import records by k_dead_pack, routed and stored behind the step's own publishes -- the
+  // import range behind the local range, its pairs appended at TS_PAIR_BASE, one sort and
+  // enqueue for both, as phase B of a sharded step.  The pass sees `d` with its receive side
+  // pointing at the dead-letter buffers (restore() and publish_host keep theirs); the counts
+  // are k_dead_pack's.  One list and one pair of buffers serve the steps in flight: the
+  // routing halves of consecutive steps are ordered on one stream, and the ingest half
+  // touches none of it
+  void launch_dead(hipStream_t s, const DS& d) {
+    Range rg("chanamq.DL.dead_pass");
+    hipLaunchKernelGGL(k_dead_pack, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
+    hipLaunchKernelGGL(k_dead_pack, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
+    DS v = d;
+    v.dlx = 2;
+    v.recv_desc = dl_h_.dead_desc;
+    v.recv_pay = dl_h_.dead_pay;
+    v.xchg = dl_h_.dead_xchg;
+    v.import_max = dead_room_;
+    v.import_bytes = dl_h_.dead_bytes;
+    launch_route(s, v, dead_room_, /*imports=*/true);
+    hipLaunchKernelGGL(k_dead_pack, capped(ceil_div(dead_room_, 256), 64), dim3(256), 0, s, d, 2u, dead_room_);
+  }
+
   // world == 1: the whole step; world > 1: phase A (ingest, local route, pack)
   void launch_main(hipStream_t s, const DS& d) {
     launch_ingest(s, d);
     launch_route(s, d, d.pub_max);   // (+ the K9 marks / K10 confirm counts: k_route_store)
-    if (d.world > 1) launch_pack(s, d);
-    else launch_tail(s, d);
+    if (d.world > 1) {
+      launch_pack(s, d);
+    } else {
+      if (d.dlx) launch_dead(s, d);
+      launch_tail(s, d);
+    }
   }
 
   // world == 1 with overlap: the routing / delivery half of the step (the step's acks /
@@ -2783,6 +2859,7 @@ class Engine {
   // never in the ingest half, so an overlapped ingest never touches delivery-side state)
   void launch_rest(hipStream_t s, const DS& d) {
     launch_route(s, d, d.pub_max);
+    if (d.dlx) launch_dead(s, d);
     launch_tail(s, d);
   }
   // the launches f makes on stream st, captured once into *ge

@@ -73,6 +73,13 @@ struct Counters {       // per-step counters (device -> host)
   u32 n_routed_msgs, n_unknown_exchange, n_ring_full, n_acked;
   u32 n_persist, n_consumed, persist_used, n_persist_overflow;
   u32 lat_hist[32];     // deliveries by (deliver_step - publish_step), last bin = overflow
+  // dead-lettering (x-dead-letter-exchange; DS.dlx): entries that joined the dead list this step
+  // by reason (the first two are also in n_expired / n_maxlen_dropped, the third in no other
+  // counter), dead letters lost (no such exchange when the entry died, or one that routed it
+  // to no queue; a record larger than the dead-letter payload buffer), and the entries
+  // pending on the list at the end of the step (a gauge).  Here, among the words k_stage zeroes
+  // with the step's other counters
+  u32 n_dl_expired, n_dl_maxlen, n_dl_rejected, n_dl_unrouted, n_dl_dropped, n_dl_pending;
   u64 log_head, log_tail;
   u32 msg_free_top, n_live_msgs;
   i64 live_bytes;       // body-log slot bytes of live messages (exact, unlike head - tail)
@@ -125,7 +132,7 @@ struct DeltaRec { u64 dst; u32 len; u32 chunk0; };
 // C entry points of one Engine (engine.hip: Engine::c_api).  All return 0 / a parity on
 // success and -1 on error (message: error()).  Parity p = the double-buffered step IO set
 // of a submitted step; its host-mapped outputs stay valid until the next submit of p.
-#define CMQ_STEP_ABI 9
+#define CMQ_STEP_ABI 10
 #define PSLOTS 4                // rotating host store-record slots (a step's records live PSLOTS - 1 more steps)
 #define UNPAUSE_STEP_MAX 1024   // connections unpaused per step (StepIn.nunp)
 struct CmqEngineApi {
