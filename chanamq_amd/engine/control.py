@@ -134,13 +134,19 @@ class ControlState:
 
     def __init__(self, c_max=1024, chpc=16, q_max=4096, x_max=1024, cons_max=16384,
                  hash_wildcard=True, ring_pool=1 << 26, default_queue_capacity=1 << 16,
-                 world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False, dead_letter=False):
+                 world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False, dead_letter=False, x_death=False):
         # chana.mq.gpu.dead-letter: a queue's x-dead-letter-exchange / x-dead-letter-routing-key are
         # honoured (off: they are ignored, as the reference does).  Single-rank planes only: the
         # exchange's queues may live on another rank, which the dead pass cannot reach yet
         self.dead_letter = bool(dead_letter)
         if self.dead_letter and world > 1:
             raise ValueError("dead_letter=True is not served on a sharded plane (world > 1)")
+        # chana.mq.gpu.dead-letter-x-death: a dead letter's property bytes get the x-death /
+        # x-first-death-* headers and lose the expiration, and a queue its history bans is refused
+        # (off: the bytes are verbatim and cycles go round)
+        self.x_death = bool(x_death)
+        if self.x_death and not self.dead_letter:
+            raise ValueError("x_death=True needs dead_letter=True")
         # chana.mq.gpu.queue-limits: a queue's x-max-length / x-overflow are honoured (off: they
         # are ignored, as the reference does)
         self.queue_limits = bool(queue_limits)

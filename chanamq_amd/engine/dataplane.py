@@ -72,8 +72,14 @@ class StepResult:
 class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
                  world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
-                 headers_match=False, queue_limits=False, dead_letter=False, **cfg):
-        """``dead_letter``: queues honour x-dead-letter-exchange / x-dead-letter-routing-key: entries
+                 headers_match=False, queue_limits=False, dead_letter=False, x_death=False, **cfg):
+        """``x_death`` (needs ``dead_letter``): the dead pass rewrites each dead letter's property
+        bytes -- x-death / x-first-death-* headers, the expiration removed (k_dead_size,
+        k_dead_pack<true>: dp_xdeath.h) -- and its routing refuses the queues the history bans
+        (cycle detection; n_dl_cycle).  Off: the bytes are verbatim and the step's launches are
+        those of ``dead_letter`` alone.
+
+        ``dead_letter``: queues honour x-dead-letter-exchange / x-dead-letter-routing-key: entries
         that expire, are trimmed by x-max-length or are rejected without requeue join the
         device's dead list and are published to the exchange by the next step's dead pass
         (k_dead_pack; engine cfg dead_max / dead_bytes bound the list and one pass's payload).
@@ -94,6 +100,8 @@ class GpuDataPlane(ControlState):
         (``step()`` does: a payload buffer is reused two steps later).  None / -1: off."""
         if dead_letter and world > 1:
             raise ValueError("dead_letter=True is not served on a sharded plane (world > 1)")
+        if x_death and not dead_letter:
+            raise ValueError("x_death=True needs dead_letter=True")
         self.mod = ops.load()
         full = dict(cfg)
         full.setdefault("egress_ref_back", -1 if egress_ref is None else int(egress_ref))
@@ -112,7 +120,7 @@ class GpuDataPlane(ControlState):
             full.setdefault("copy_engine", 3)
         full.update(device=device, hash_wildcard=int(hash_wildcard), graph=int(graph), world=world, rank=rank,
                     exchange_lag=int(exchange_lag), queue_limits=int(bool(queue_limits)),
-                    dead_letter=int(bool(dead_letter)))
+                    dead_letter=int(bool(dead_letter)), x_death=int(bool(x_death)))
         self.eng = self.mod.Engine(full)
         self.info = self.eng.info()
         sz = self.info["sizeof"]
@@ -168,7 +176,7 @@ class GpuDataPlane(ControlState):
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
                          shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits,
-                         dead_letter=dead_letter)
+                         dead_letter=dead_letter, x_death=x_death)
 
     # ================================================================== uploads
     # ``defer`` (set by the broker around control work done while steps keep running): table
@@ -500,6 +508,12 @@ class GpuDataPlane(ControlState):
         row[:len(name)] = np.frombuffer(name, np.uint8)
         row[256:256 + len(key)] = np.frombuffer(key, np.uint8)
         self._write("q_dl_name", row, q.slot * 512)
+        if self.x_death:   # the queue's own name and vhost, for its dead letters' x-death entries
+            own = q.name.encode("utf-8", "surrogateescape")
+            row = np.zeros(256, np.uint8)
+            row[:len(own)] = np.frombuffer(own, np.uint8)
+            self._write("q_name", row, q.slot * 256)
+            self._up_at("q_name_len", len(own) | (self.vhosts[q.vhost] << 8), q.slot, np.uint32)
         self._up_at("q_dl_len", len(name) | (len(key) << 8) | (0x10000 if q.dlk is not None else 0), q.slot, np.uint32)
         slot = self.dlx_slot(q)
         self._up_at("q_dlx", 1 if slot is None else slot + 2, q.slot, np.uint32)

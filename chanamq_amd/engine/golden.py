@@ -14,6 +14,7 @@ import numpy as np
 
 from ..models.matcher import topic_match
 from ..protocol import constants as C
+from . import xdeath
 from .control import ControlState
 from .layout import (MF_HAS_TS, MF_PERSIST, RDESC, SS_CTRL, SS_FRAME_ERROR, SS_OVERFLOW, SS_TOO_LARGE,
                      SS_UNEXPECTED)
@@ -212,8 +213,10 @@ class GoldenDataPlane(ControlState):
     def queue_dlx_changed(self, q):
         # the device's per-slot row of exchange name and key (q_dl_name / q_dl_len): written when a
         # queue with a pair takes the slot, left as it is otherwise, read by the dead pass
+        # (x_death: and the queue's own name and vhost -- q_name / q_name_len)
         if q.dlx is not None:
-            self._dl_row[q.slot] = (q.dlx.encode("utf-8", "surrogateescape"), q.dlk)
+            self._dl_row[q.slot] = (q.dlx.encode("utf-8", "surrogateescape"), q.dlk,
+                                    q.name.encode("utf-8", "surrogateescape"), q.vhost)
 
     def _dead_join(self, msg, q, qpos, reason, xs, step, ch=0, tag=0):
         """The entry joins the dead list in place of its release (the list holds the reference).
@@ -249,9 +252,21 @@ class GoldenDataPlane(ControlState):
         take = nrec = nbytes = 0
         for it in items:
             m = it["msg"]
-            it["ex"], it["rk"] = self._dl_row[it["q"]]
+            it["ex"], it["rk"], qname, vhost = self._dl_row[it["q"]]
             rk = m.rk if it["rk"] is None else it["rk"]
-            it["size"] = a16(a16(len(it["ex"]) + len(rk) + len(m.props)) + len(m.body))
+            it["props"], it["bans"], over = m.props, [], False
+            if self.x_death:
+                # the new property bytes (k_dead_size: the prefix is that of the new sizes) and the
+                # queues the history bans, by name in the source queue's vhost (unknown names: ignored)
+                st, it["props"], names = xdeath.rewrite(m.props, qname, it["reason"], m.ex, m.rk, max(now_ms, 0) // 1000)
+                over = st == xdeath.OVER
+                for nm in names:
+                    bq = self.queues.get((vhost, nm.decode("utf-8", "surrogateescape"))) if 0 < len(nm) < 256 else None
+                    if bq is not None:
+                        it["bans"].append(bq.slot)
+            it["size"] = a16(a16(len(it["ex"]) + len(rk) + len(it["props"])) + len(m.body))
+            if over:   # (over a limit of the rewrite: taken without a record, like one larger than the buffer)
+                it["size"] = self.dead_bytes + 1
             if it["size"] <= self.dead_bytes:   # (larger than the whole buffer: taken without a record)
                 if nrec >= self.dead_room or nbytes + it["size"] > self.dead_bytes:
                     break
@@ -267,11 +282,14 @@ class GoldenDataPlane(ControlState):
                 continue
             rk = m.rk if it["rk"] is None else it["rk"]
             x = self.exch_by_slot.get(it["xs"])
-            qs = self._route(x, rk, m.props) if x is not None else []
+            qs = self._route(x, rk, it["props"]) if x is not None else []
+            if it["bans"]:   # cycle detection: a banned queue is refused, the others still get it
+                cnt["n_dl_cycle"] += sum(1 for q in qs if q in it["bans"])
+                qs = [q for q in qs if q not in it["bans"]]
             if not qs:
                 cnt["n_dl_unrouted"] += 1
             else:   # a new message: new id, no channel, never expiring again by its own property
-                new = _Msg(it["ex"], rk, m.props, m.body, len(qs), self.step_no, m.flags & MF_PERSIST, ts=m.ts,
+                new = _Msg(it["ex"], rk, it["props"], m.body, len(qs), self.step_no, m.flags & MF_PERSIST, ts=m.ts,
                            mid=self._mid())
                 self._enqueue(new, qs, 0, now_ms)
             self._release(m)

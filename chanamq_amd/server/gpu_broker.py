@@ -220,7 +220,7 @@ class GpuBroker:
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
                  persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False,
-                 dead_letter=False):
+                 dead_letter=False, x_death=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -250,6 +250,13 @@ class GpuBroker:
             raise ValueError("dead_letter=True needs a data plane built with dead_letter=True")
         if self.dead_letter and node is not None:
             raise ValueError("dead_letter=True is not served on a sharded node")
+        # x-death headers and cycle detection (chana.mq.gpu.dead-letter-x-death): the plane's work
+        # (built with x_death=True); here only the dl_cycle statistic
+        self.x_death = bool(x_death)
+        if self.x_death and not self.dead_letter:
+            raise ValueError("x_death=True needs dead_letter=True")
+        if self.x_death and not getattr(plane, "x_death", False):
+            raise ValueError("x_death=True needs a data plane built with x_death=True")
         native_x = bool(getattr(plane, "native_xchg", False))
         if io == "auto":
             io = "pipeline" if (hasattr(plane, "eng") and (node is None or native_x)) else "native"
@@ -362,6 +369,8 @@ class GpuBroker:
             self.stats.update(maxlen_dropped=0, maxlen_rejected=0)
         if self.dead_letter:
             self.stats.update(dict.fromkeys(self.DL_STATS, 0))
+        if self.x_death:
+            self.stats["dl_cycle"] = 0
         self.lock = _PlaneLock(self)
         self.light = _LightLock(self.lock)
 
@@ -825,6 +834,8 @@ class GpuBroker:
             self.stats.update(maxlen_dropped=st.get("maxlen_dropped", 0), maxlen_rejected=st.get("maxlen_rejected", 0))
         if self.dead_letter:
             self.stats.update({k: st.get(k, 0) for k in self.DL_STATS})
+        if self.x_death:
+            self.stats["dl_cycle"] = st.get("dl_cycle", 0)
         if st.get("spill_moved"):
             self.stats["spilled_bytes"] = st["spill_moved"]
         self._fe_stats = st
@@ -1254,6 +1265,8 @@ class GpuBroker:
             for k in self.DL_STATS[:-1]:
                 self.stats[k] += cnt.get("n_" + k, 0)
             self.stats["dl_pending"] = cnt.get("n_dl_pending", 0)
+        if self.x_death:   # (dead letter, queue) pairs refused: the queue is in the dead letter's own history
+            self.stats["dl_cycle"] += cnt.get("n_dl_cycle", 0)
         for conn, code, chslot in events:
             c = self.conns.get(conn)
             if c is None or c.state != "open":

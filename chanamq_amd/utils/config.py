@@ -296,6 +296,12 @@ class Config:
         dead_letter = bool(g(k + "dead-letter", False))
         if dead_letter:
             plane.update(dead_letter=True, dead_max=int(g(k + "dead-max", 1024)), dead_bytes=int(g(k + "dead-bytes", 8 << 20)))
+        # dead letters carry x-death / x-first-death-* headers and cycles are refused (needs dead-letter)
+        x_death = bool(g(k + "dead-letter-x-death", False))
+        if x_death:
+            if not dead_letter:
+                raise ValueError("chana.mq.gpu.dead-letter-x-death needs chana.mq.gpu.dead-letter")
+            plane.update(x_death=True)
         hi = int(g("chana.mq.flow.memory-high-watermark", -1))
         lo = int(g("chana.mq.flow.memory-low-watermark", -1))
         if hi < 0:   # 40% of what the broker can hold: the HBM body log + the host spill ring
@@ -307,7 +313,7 @@ class Config:
                       confirm_read=int(g(k + "confirm-read", 128 << 10)),
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
-                      headers_match=headers_match, queue_limits=queue_limits, dead_letter=dead_letter,
+                      headers_match=headers_match, queue_limits=queue_limits, dead_letter=dead_letter, x_death=x_death,
                       mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 

@@ -1308,6 +1308,7 @@ void Frontend::finish_oldest(std::deque<Inflight>& inflight) {
     stats_.dl_unrouted += c.n_dl_unrouted;
     stats_.dl_dropped += c.n_dl_dropped;
     stats_.dl_pending = c.n_dl_pending;
+    stats_.dl_cycle += c.n_dl_cycle;
     stats_.ctrl += c.n_ctrl;
     stats_.live_msgs = c.n_live_msgs;
     stats_.log_used = c.log_head - c.log_tail;

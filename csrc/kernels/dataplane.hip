@@ -157,6 +157,7 @@ __global__ __launch_bounds__(1024) void k_stage(DS d) {
 
 #include "dp_frame_scan.h"
 #include "dp_headers.h"
+#include "dp_xdeath.h"
 
 // ============================================================================ K3 classify / decode
 DEV void set_counts(const DS& d, u32 np, u32 na) {
@@ -1077,9 +1078,22 @@ struct RouteAcc {
 
 // emit one candidate queue per lane (valid lanes), preserving lane order.  qo / qc: the
 // queue's owner and consumer count when the caller loaded them already (INVALID: load)
+// BAN (the dead view's routing with x-death on): a queue the record's history bans is no
+// candidate at all -- counted (n_dl_cycle, pass 0) and otherwise as if its binding were not there.
+// The dead pass's record of publish p: its records follow the step's own publishes.  Pass 0 runs
+// inside k_import_route, whose block 0 writes tot[TS_RANGE_LO] while the other blocks already
+// route: there the base is n_pubs, as for import_one; pass 1 is a later kernel
 template <int PASS>
+DEV u32 ban_record(const DS& d, u32 p) { return p - (PASS == 0 ? d.ctr->n_pubs : d.tot[TS_RANGE_LO]); }
+template <int PASS, bool BAN = false>
 DEV void route_emit(const DS& d, RouteAcc<PASS>& a, u32 p, u32 wbase, u32 srank, u32 q, bool valid, u32 lane,
                     u32 qo = INVALID, u32 qc = INVALID) {
+  if (BAN) {
+    const bool b = valid && xd_banned(d, ban_record<PASS>(d, p), q);
+    const u64 bm = __ballot(b);
+    if (PASS == 0 && lane == 0 && bm) atomicAdd(&d.ctr->n_dl_cycle, (u32)__popcll(bm));
+    valid = valid && !b;
+  }
   const u32 me = d.my_rank;
   u32 owner = (valid && d.world > 1) ? (qo != INVALID ? qo : d.q_owner[q]) : me;
   bool remote = valid && owner != me;
@@ -1157,11 +1171,12 @@ DEV bool hop_next(HopWalk& h, u32& x, u32 lane) {
 }
 
 // the walk is over: its queues through route_emit, the local ones kept for pass 1
+template <bool BAN = false>
 DEV void hop_finish(const DS& d, RouteAcc<0>& a, const HopWalk& h, const Pub& pb, u32 p, u32 srank, u32 lane) {
   __builtin_amdgcn_wave_barrier();
   for (u32 k0 = 0; k0 < h.nl; k0 += 64) {
     const bool v = k0 + lane < h.nl;
-    route_emit<0>(d, a, p, 0, srank, v ? h.L[k0 + lane] : 0u, v, lane);
+    route_emit<0, BAN>(d, a, p, 0, srank, v ? h.L[k0 + lane] : 0u, v, lane);
   }
   // more than 8 local queues: a run of hop_q for pass 1.  Only a publish that is enqueued
   // reserves (an immediate publish without a consumer is returned with 313: no pairs), so
@@ -1183,7 +1198,8 @@ DEV void hop_finish(const DS& d, RouteAcc<0>& a, const HopWalk& h, const Pub& pb
   for (u32 k0 = 0; k0 < h.nl; k0 += 64) {
     const bool v = k0 + lane < h.nl;
     const u32 q = v ? h.L[k0 + lane] : 0u;
-    const bool local = v && (d.world > 1 ? d.q_owner[q] : d.my_rank) == d.my_rank;
+    bool local = v && (d.world > 1 ? d.q_owner[q] : d.my_rank) == d.my_rank;
+    if (BAN) local = local && !xd_banned(d, ban_record<0>(d, p), q);   // (as route_emit refused it above)
     const u64 lm = __ballot(local);
     if (local) d.hop_q[off + n + (u32)__popcll(lm & lanemask_lt())] = q;
     n += (u32)__popcll(lm);
@@ -1196,7 +1212,7 @@ DEV void hop_finish(const DS& d, RouteAcc<0>& a, const HopWalk& h, const Pub& pb
   if (lane == 0) d.pub_qc[(u64)p * PUB_QC] = XT_EDGE | off;
 }
 
-template <int PASS>
+template <int PASS, bool BAN = false>
 DEV void route_one(const DS& d, u32 p, u32 lane) {
   Pub& pb = d.pubs[p];
   // pass 0 of an imported record that arrived with its queue ran in import_one
@@ -1228,7 +1244,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
   RouteAcc<PASS> a;
   const i32 ex = pb.exch;
   if (pb.flags & (MF_RESTORE | MF_ONEQ)) {   // recovered / origin-routed: exactly its queue
-    route_emit<PASS>(d, a, p, wbase, srank, (u32)pb.keyhash, lane == 0, lane);
+    route_emit<PASS, BAN>(d, a, p, wbase, srank, (u32)pb.keyhash, lane == 0, lane);
   } else if (ex >= 0) {
     u32 xt = d.x_type[ex];
     // a walk over exchange-to-exchange edges (pass 0; pass 1 was served from pub_qc / hop_q
@@ -1263,7 +1279,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
           bool v = k0 + lane < c;
           u32 q = v ? list[o + k0 + lane] : 0;
           if (__builtin_expect(hop, 0)) hop_add(h, q, v, lane);
-          else route_emit<PASS>(d, a, p, wbase, srank, q, v, lane);
+          else route_emit<PASS, BAN>(d, a, p, wbase, srank, q, v, lane);
         }
         if (hop) {
           const u32* xl = xt == EX_DIRECT ? d.d_x : d.fan_x;
@@ -1325,7 +1341,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
           u32 qtop = (u32)__shfl((int)q, hm ? 63 - __clzll(hm) : 0);     // highest hit
           bool emit = hit && (below ? qb : lastq) != q;
           if (__builtin_expect(hop, 0)) hop_add(h, q, emit, lane);
-          else route_emit<PASS>(d, a, p, wbase, srank, q, emit, lane, qo, qc);
+          else route_emit<PASS, BAN>(d, a, p, wbase, srank, q, emit, lane, qo, qc);
           if (hm) lastq = qtop;
         }
       }
@@ -1333,7 +1349,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
       xt = d.x_type[x] & (XF_TYPE | XF_HMATCH);
     }
     if constexpr (PASS == 0) {
-      if (hop) hop_finish(d, a, h, pb, p, srank, lane);
+      if (hop) hop_finish<BAN>(d, a, h, pb, p, srank, lane);
     }
   }
   if (PASS == 0 && lane == 0) {
@@ -1387,11 +1403,12 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
 
 // routing pass 0 of the group of 16 publishes [g0, g0 + 16) below n by a 1024-thread block:
 // the group's topic prefilter tiles, then wave w routes publish g0 + w
+template <bool BAN = false>
 DEV void route_group(const DS& d, u32 g0, u32 n, u32 w, u32 lane) {
   topic_group(d, g0, n, w, lane);
   __threadfence_block();
   __syncthreads();
-  if (g0 + w < n) route_one<0>(d, g0 + w, lane);
+  if (g0 + w < n) route_one<0, BAN>(d, g0 + w, lane);
   __syncthreads();   // the next group's tiles overwrite nothing this group reads, but keep waves together
 }
 
@@ -1495,7 +1512,7 @@ DEV void write_slot(u8* dst, const u8* w, const Pub& pb, const Frag* frags) {
 // fill its MsgEnt and copy exchange / rk / props / body into the log (fused k_route<1> +
 // k_store: one pass over the phase's publishes)
 DEV void store_one_pre(const DS& d, u32 p, u32 lane, const Pub& pb, u32 nq, u32 rr, u32 soff, u32 wbase);
-template <bool DLX>
+template <bool DLX, bool BAN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_route_store(DS d, u32 marks) {
   u32 lane = lane_id();
   if (blockIdx.x == 0 && threadIdx.x < 64) live_add_blocks(d, lane);
@@ -1514,7 +1531,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     const u32 rr = d.pub_routed_rank[p];
     const u32 soff = d.pub_slot_off[p];
     const u32 wbase = d.tot[TS_PAIR_BASE] + d.pub_pair_off[p];
-    route_one<1>(d, p, lane);
+    route_one<1, BAN>(d, p, lane);
     store_one_pre(d, p, lane, pb, nq, rr, soff, wbase);
   }
 }
@@ -1764,6 +1781,7 @@ DEV void pack_one(const DS& d, u32 p, u32 lane, const u32* s_base) {
 // at once)
 DEV void import_one(const DS& d, u32 i, const u32* xr);
 DEV void link_ack_one(const DS& d, u32 i);
+template <bool BAN>   // (the dead view's launch with x-death on: route_emit's ban check)
 __global__ __launch_bounds__(1024) void k_import_route(DS d) {
   __shared__ u32 xr[4 * WORLD_MAX];
   __shared__ u32 s_n, s_k;
@@ -1808,7 +1826,7 @@ __global__ __launch_bounds__(1024) void k_import_route(DS d) {
     if (tid < 16 && g0 + tid < n) import_one(d, g0 + tid, xr);
     __threadfence_block();
     __syncthreads();
-    route_group(d, base + g0, base + n, w, lane);
+    route_group<BAN>(d, base + g0, base + n, w, lane);
   }
 }
 
@@ -1897,7 +1915,8 @@ DEV bool dead_key_less(const u64* a, const u64* b) {
   return a[3] < b[3];
 }
 // record bytes of item `it` in slot layout (0: a hole); *lens = exchange name | key << 8 bytes
-DEV u32 dead_rec_size(const DS& d, const DeadItem& it, u32* lens, bool* cold) {
+// (plen: the property bytes the record gets -- x-death's new length; INVALID: the message's own)
+DEV u32 dead_rec_size(const DS& d, const DeadItem& it, u32* lens, bool* cold, u32 plen = INVALID) {
   *lens = 0;
   *cold = false;
   if (it.msg == INVALID) return 0;
@@ -1906,8 +1925,11 @@ DEV u32 dead_rec_size(const DS& d, const DeadItem& it, u32* lens, bool* cold) {
   const u32 exl = ql & 255u, rkl = (ql & DLQ_HAS_KEY) ? ((ql >> 8) & 255u) : (u32)m.rk_len;
   *lens = exl | (rkl << 8);
   *cold = (m.log_off & COLD_BIT) != 0;
-  return align16(align16(exl + rkl + m.props_len) + m.body_len);
+  return align16(align16(exl + rkl + (plen != INVALID ? plen : (u32)m.props_len)) + m.body_len);
 }
+// XD (DlState.xdeath): the sizes are k_dead_size's, phase 1 rewrites the property bytes and fills
+// the record's ban row (dp_xdeath.h); without it the kernel is the one it was
+template <bool XD>
 __global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
   const u32 tid = threadIdx.x, lane = lane_id();
   if (phase == 0) {
@@ -1943,14 +1965,18 @@ __global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
     // thread t: the item at ordered position t (read before anything is written back)
     DeadItem it;
     it.msg = INVALID; it.q = 0; it.qpos = 0; it.step = 0; it.reason = 0; it.ch = 0; it.xs = 0; it.tag = 0;
-    u32 sz = 0, lens = 0;
-    bool cold = false;
+    u32 sz = 0, lens = 0, plen = INVALID;
+    bool cold = false, over = false;
     if (tid < n) {
       it = d.dl->dead[perm[tid]];
-      sz = dead_rec_size(d, it, &lens, &cold);
+      if (XD) {   // (INVALID: the rewrite is over a limit -- dropped like a record larger than the buffer)
+        plen = d.dl->dead_plen[perm[tid]];
+        over = plen == INVALID;
+      }
+      sz = dead_rec_size(d, it, &lens, &cold, plen);
     }
     const bool hole = tid < n && it.msg == INVALID;
-    const bool drop = tid < n && !hole && (cold || (u64)sz > d.dl->dead_bytes);
+    const bool drop = tid < n && !hole && (cold || over || (u64)sz > d.dl->dead_bytes);
     const bool rec = tid < n && !hole && !drop;
     u32 tot_b, tot_r;
     const u32 off = block_scan<1024>(rec ? sz : 0u, lds, tot_b);
@@ -1963,6 +1989,7 @@ __global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
       d.dl->dead_take[tid] = it;
       d.dl->dead_off[2 * tid] = rec ? ri : INVALID;
       d.dl->dead_off[2 * tid + 1] = off;
+      if (XD) d.dl->dead_plen[tid] = plen;   // (every read of the list-order values lies before the barrier above)
       if (drop) atomicAdd(&d.ctr->n_dl_dropped, 1u);
     } else if (tid < n) {
       d.dl->dead[tid - take] = it;
@@ -2006,14 +2033,26 @@ __global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
       u8* dst = d.dl->dead_pay + off;
       wave_copy(dst, names, exl);
       wave_copy(dst + exl, own ? slot + m.ex_len : names + DLQ_STR, rkl);
-      wave_copy(dst + exl + rkl, slot + m.ex_len + m.rk_len, m.props_len);
-      wave_copy(dst + align16(exl + rkl + m.props_len), slot + m.body_off, m.body_len);
+      u32 plen = m.props_len;
+      bool bad = false;
+      if (XD) {
+        u32* ban_n = d.dl->dead_ban_n + ri;
+        plen = xd_render(d, it, m, slot, dst + exl + rkl, d.dl->dead_plen[t], d.dl->dead_ban + (u64)ri * XD_ELEMS_MAX, ban_n, lane);
+        bad = plen == INVALID;   // (the two passes disagree: never; the record then names no exchange and carries nothing)
+        if (bad) {
+          plen = 0;
+          if (lane == 0) *ban_n = 0;
+        }
+      } else {
+        wave_copy(dst + exl + rkl, slot + m.ex_len + m.rk_len, m.props_len);
+      }
+      if (!bad) wave_copy(dst + align16(exl + rkl + plen), slot + m.body_off, m.body_len);
       if (lane == 0) {
         RDesc rd{};
         rd.pay_off = off;
-        rd.body_len = m.body_len;
-        rd.props_len = m.props_len;
-        rd.exch = (i32)it.xs;
+        rd.body_len = bad ? 0u : m.body_len;
+        rd.props_len = plen;
+        rd.exch = bad ? -1 : (i32)it.xs;
         // a new message without a publisher: never mandatory or immediate, never expiring again
         // by its own property (the target queue's x-message-ttl still applies at its enqueue)
         rd.flags = (m.flags & (MF_PERSIST | MF_HAS_TS)) | MF_SLOTFMT;
@@ -2021,7 +2060,7 @@ __global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
         rd.rk_len = (u8)rkl;
         rd.expire_ms = 0;
         rd.ts_ms = m.ts_ms;
-        rd.pad[0] = it.q;        // (source queue and reason: for x-death, later)
+        rd.pad[0] = it.q;        // (source queue and reason: read by nothing; x-death works from the item itself)
         rd.pad[1] = it.reason;
         d.dl->dead_desc[ri] = rd;
       }

@@ -57,6 +57,8 @@ DEV int hdr_fixed(u32 tag) {
 DEV bool hdr_is_raw(u32 tag) { return tag == 'f' || tag == 'd' || tag == 'D' || tag == 'A' || tag == 'F'; }
 DEV bool hdr_is_str(u32 tag) { return tag == 'S' || tag == 'x'; }
 
+// (xdeath_plan.h keeps a host-compilable copy of hdr_fixed / hdr_next, xd_fixed / xd_next: a change
+// of the table format goes into both)
 // the entry at pos of the table ending at end, pos moved behind it; false: malformed (an
 // unknown tag, or the entry runs past the table).  voff / vlen: the bytes the canonical
 // value is made of (a string's bytes; an array's or table's length and bytes)

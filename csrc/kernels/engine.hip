@@ -204,11 +204,13 @@ class Engine {
     // import buffers.  The pass's records run through the import path of a world-1 engine
     // (publish slots and fragments past the step's own: pub_cap, frag_max + i), so it takes
     // at most import_max of them a step
+    if (get("x_death", 0) && !get("dead_letter", 0)) throw std::runtime_error("x_death needs dead_letter");
     d_.dlx = get("dead_letter", 0) ? 1u : 0u;
     if (d_.dlx) {
       if (d_.world != 1)
         throw std::runtime_error("dead_letter: single-rank planes only (a dead-letter exchange's queues may live on "
                                  "another rank, which needs the cross-rank pack path)");
+      dl_h_.xdeath = get("x_death", 0) ? 1u : 0u;
       dl_h_.dead_max = (u32)get("dead_max", 1024);
       dl_h_.dead_bytes = get("dead_bytes", 8ull << 20);
       if (dl_h_.dead_max < 1 || dl_h_.dead_max > DEAD_LIST_MAX)
@@ -511,6 +513,13 @@ class Engine {
       dl_h_.dead_desc = (RDesc*)dev("dead_desc", sizeof(RDesc) * (u64)dl_h_.dead_max);
       dl_h_.dead_pay = (u8*)dev("dead_pay", dl_h_.dead_bytes + 64);
       dl_h_.dead_xchg = (u32*)dev("dead_xchg", 4ull * XC_WORDS);
+      if (dl_h_.xdeath) {
+        dl_h_.q_name = (u8*)dev("q_name", (u64)DLQ_STR * d_.q_max);
+        dl_h_.q_name_len = (u32*)dev("q_name_len", 4ull * d_.q_max);
+        dl_h_.dead_plen = (u32*)dev("dead_plen", 4ull * dl_h_.dead_max);
+        dl_h_.dead_ban = (u32*)dev("dead_ban", 4ull * XD_ELEMS_MAX * dead_room_);
+        dl_h_.dead_ban_n = (u32*)dev("dead_ban_n", 4ull * dead_room_);
+      }
       DlState* dl = (DlState*)dev("dl_state", sizeof(DlState));
       HIPCHECK(hipMemcpy(dl, &dl_h_, sizeof(DlState), hipMemcpyHostToDevice));
       d_.dl = dl;
@@ -1002,7 +1011,7 @@ class Engine {
     o["egress_tail_engine"] = engine_no(copy_mode_ == 3, (u32)tail_engine_);
     o["h2d_split_min"] = h2d_split_min_;
     o["queue_limits"] = d_.limits;
-    o["dead_letter"] = d_.dlx; o["dead_max"] = dl_h_.dead_max; o["dead_bytes"] = dl_h_.dead_bytes; o["dead_room"] = dead_room_;
+    o["dead_letter"] = d_.dlx; o["dead_max"] = dl_h_.dead_max; o["dead_bytes"] = dl_h_.dead_bytes; o["dead_room"] = dead_room_; o["x_death"] = dl_h_.xdeath;
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
     o["restore_max"] = restore_max_;
     o["xfer_desc_max"] = d_.xfer_desc_max; o["xfer_bytes"] = d_.xfer_bytes; o["world_max"] = WORLD_MAX;
@@ -1603,6 +1612,7 @@ class Engine {
     // (only with dead_letter on: off, a step's counters are the dict they were -- each entry is a
     // string and a hash on the host's per-step path, which the headline benchmark drives)
     if (d_.dlx) { F(n_dl_expired); F(n_dl_maxlen); F(n_dl_rejected); F(n_dl_unrouted); F(n_dl_dropped); F(n_dl_pending); }
+    if (dl_h_.xdeath) F(n_dl_cycle);
 #undef F
     std::vector<u32> lat(c.lat_hist, c.lat_hist + LAT_BINS);
     o["lat_hist"] = lat;
@@ -2725,13 +2735,15 @@ class Engine {
 
   // route + store the publishes of the current phase range (K6); nmax = range capacity.
   // imports: phase B's import + routing pass 0 kernel (k_import_route) instead of k_route
-  void launch_route(hipStream_t s, const DS& d, u32 nmax, bool imports = false) {
+  // ban: the dead view's routing with x-death on (the instantiations with route_emit's ban check)
+  void launch_route(hipStream_t s, const DS& d, u32 nmax, bool imports = false, bool ban = false) {
     Range rg("chanamq.K6-K13.route_store");
     // 16 publishes per block, grid-stride; the grid is the blocks that can be resident
     // (k_route: 2 per CU at 64 VGPRs; k_import_route: 1), not the capacity's groups --
     // the idle blocks of a capacity-sized grid were still dispatched after the busy ones
     const u64 ngroups = ceil_div(nmax ? nmax : 1, 16);
-    if (imports) hipLaunchKernelGGL(k_import_route, capped(ngroups, n_cu_), dim3(1024), 0, s, d);   // + prep, link acks
+    if (imports && ban) hipLaunchKernelGGL(k_import_route<true>, capped(ngroups, n_cu_), dim3(1024), 0, s, d);
+    else if (imports) hipLaunchKernelGGL(k_import_route<false>, capped(ngroups, n_cu_), dim3(1024), 0, s, d);   // + prep, link acks
     else hipLaunchKernelGGL(k_route, capped(ngroups, 2 * n_cu_), dim3(1024), 0, s, d);
     // scan of the routing counts + the phase's log reservation, then pairs + store
     const ScanArgs a = scan_args({{d.pub_nq, d.pub_pair_off}, {d.pub_slot, d.pub_slot_off},
@@ -2741,7 +2753,8 @@ class Engine {
                        scan_status_, scan_ctl_, scan_smax_, d);
     // (the kernels that hold dead-letter code exist twice: with the flag off the step runs the
     // instantiation without any of it)
-    if (d.dlx) hipLaunchKernelGGL(k_route_store<true>, wave_blocks(nmax), dim3(256), 0, s, d, imports ? 0u : 1u);
+    if (ban) hipLaunchKernelGGL((k_route_store<true, true>), wave_blocks(nmax), dim3(256), 0, s, d, 0u);
+    else if (d.dlx) hipLaunchKernelGGL(k_route_store<true>, wave_blocks(nmax), dim3(256), 0, s, d, imports ? 0u : 1u);
     else hipLaunchKernelGGL(k_route_store<false>, wave_blocks(nmax), dim3(256), 0, s, d, imports ? 0u : 1u);
   }
 
@@ -2829,8 +2842,17 @@ class Engine {
   // touches none of it
   void launch_dead(hipStream_t s, const DS& d) {
     Range rg("chanamq.DL.dead_pass");
-    hipLaunchKernelGGL(k_dead_pack, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
-    hipLaunchKernelGGL(k_dead_pack, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
+    // x-death: one launch more, the pending items' new property lengths, before phase 0 takes its
+    // prefix by them; phase 1 then rewrites the bytes and fills the ban rows the routing reads
+    const bool xd = dl_h_.xdeath != 0;
+    if (xd) {
+      hipLaunchKernelGGL(k_dead_size, wave_blocks(dl_h_.dead_max), dim3(256), 0, s, d);
+      hipLaunchKernelGGL(k_dead_pack<true>, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
+      hipLaunchKernelGGL(k_dead_pack<true>, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
+    } else {
+      hipLaunchKernelGGL(k_dead_pack<false>, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
+      hipLaunchKernelGGL(k_dead_pack<false>, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
+    }
     DS v = d;
     v.dlx = 2;
     v.recv_desc = dl_h_.dead_desc;
@@ -2838,8 +2860,8 @@ class Engine {
     v.xchg = dl_h_.dead_xchg;
     v.import_max = dead_room_;
     v.import_bytes = dl_h_.dead_bytes;
-    launch_route(s, v, dead_room_, /*imports=*/true);
-    hipLaunchKernelGGL(k_dead_pack, capped(ceil_div(dead_room_, 256), 64), dim3(256), 0, s, d, 2u, dead_room_);
+    launch_route(s, v, dead_room_, /*imports=*/true, /*ban=*/xd);
+    hipLaunchKernelGGL(k_dead_pack<false>, capped(ceil_div(dead_room_, 256), 64), dim3(256), 0, s, d, 2u, dead_room_);
   }
 
   // world == 1: the whole step; world > 1: phase A (ingest, local route, pack)

@@ -80,6 +80,9 @@ struct Counters {       // per-step counters (device -> host)
   // pending on the list at the end of the step (a gauge).  Here, among the words k_stage zeroes
   // with the step's other counters
   u32 n_dl_expired, n_dl_maxlen, n_dl_rejected, n_dl_unrouted, n_dl_dropped, n_dl_pending;
+  // x-death (DlState.xdeath): (dead letter, queue) pairs the dead pass's routing refused because
+  // the dead letter's history bans the queue (a cycle without a reject in it)
+  u32 n_dl_cycle, dl_pad;
   u64 log_head, log_tail;
   u32 msg_free_top, n_live_msgs;
   i64 live_bytes;       // body-log slot bytes of live messages (exact, unlike head - tail)
@@ -132,7 +135,7 @@ struct DeltaRec { u64 dst; u32 len; u32 chunk0; };
 // C entry points of one Engine (engine.hip: Engine::c_api).  All return 0 / a parity on
 // success and -1 on error (message: error()).  Parity p = the double-buffered step IO set
 // of a submitted step; its host-mapped outputs stay valid until the next submit of p.
-#define CMQ_STEP_ABI 10
+#define CMQ_STEP_ABI 11
 #define PSLOTS 4                // rotating host store-record slots (a step's records live PSLOTS - 1 more steps)
 #define UNPAUSE_STEP_MAX 1024   // connections unpaused per step (StepIn.nunp)
 struct CmqEngineApi {
