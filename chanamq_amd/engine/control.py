@@ -47,6 +47,9 @@ class Exchange:
     # their arguments (models/matcher.py canon_args): [(queue slot | dst exchange slot, key bytes, args)]
     hbindings: list = field(default_factory=list)
     hxbindings: list = field(default_factory=list)
+    # alternate-exchange (alternate_exchange on): the exchange's name, looked up in this
+    # exchange's vhost whenever the routing tables are built (it need not exist)
+    alt: Optional[str] = None
 
 
 @dataclass
@@ -134,7 +137,13 @@ class ControlState:
 
     def __init__(self, c_max=1024, chpc=16, q_max=4096, x_max=1024, cons_max=16384,
                  hash_wildcard=True, ring_pool=1 << 26, default_queue_capacity=1 << 16,
-                 world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False, dead_letter=False, x_death=False):
+                 world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False, dead_letter=False, x_death=False,
+                 alternate_exchange=False):
+        # chana.mq.gpu.alternate-exchange: Exchange.Declare's alternate-exchange argument is honoured
+        # -- an exchange the walk matched without any destination hands the publish to the exchange
+        # it names (route_closure has the rule; off: the argument is ignored, as the reference does)
+        self.alternate_exchange = bool(alternate_exchange)
+        self.alt_taken = 0   # (publish, exchange) pairs whose alternate route_closure took, ever
         # chana.mq.gpu.dead-letter: a queue's x-dead-letter-exchange / x-dead-letter-routing-key are
         # honoured (off: they are ignored, as the reference does).  Single-rank planes only: the
         # exchange's queues may live on another rank, which the dead pass cannot reach yet
@@ -259,7 +268,14 @@ class ControlState:
                          internal=False, arguments=None, passive=False, _sync=True):
         key = (vhost, name)
         x = self.exchanges.get(key)
+        alt = self.check_alternate(arguments) if self.alternate_exchange and not passive else None
         if x is not None:
+            # a declare of an existing exchange returns its slot; with alternate_exchange on, one
+            # that names another alternate than the exchange's is refused, one that names none is
+            # the no-op it always was (the rule of a queue's length limit and dead-letter pair)
+            if alt is not None and x.alt != alt:
+                raise ControlError(C.PRECONDITION_FAILED, f"exchange '{name}' is declared with "
+                                   f"alternate-exchange {x.alt!r}", 40, 10)
             return x.slot
         if passive:
             raise ControlError(C.NOT_FOUND, f"no exchange '{name}' in vhost '{vhost}'", 40, 10)
@@ -268,17 +284,54 @@ class ControlState:
         if not self._free_x:
             raise ControlError(C.RESOURCE_ERROR, "exchange table full", 40, 10)
         slot = self._free_x.pop()
-        x = Exchange(slot, vhost, name, type_, durable, auto_delete, internal, dict(arguments or {}))
+        x = Exchange(slot, vhost, name, type_, durable, auto_delete, internal, dict(arguments or {}), alt=alt)
         self.exchanges[key] = x
         self.exch_by_slot[slot] = x
         if name == "":  # default exchange: implicit binding of every queue by name
             for q in self.queues.values():
                 if q.vhost == vhost:
                     x.bindings.append((q.slot, q.name.encode()))
+        if self.alternate_exchange:
+            # this declare resolves x's own alternate, if that exists, and the alternate of every
+            # exchange that names x: each pair is a key-blind edge of the device walk, held to the
+            # walk's limits like one (506, and the declare is undone: nothing else has changed yet)
+            pairs = [(x, self._alt_of(x))] + [(y, x) for y in self.exchanges.values()
+                                              if y.alt == name and y.vhost == vhost and y is not x]
+            pairs = [(a, b) for a, b in pairs if b is not None]
+            why = None
+            if any(a.slot >= self.hop_xslots or b.slot >= self.hop_xslots for a, b in pairs):
+                why = f"alternate exchanges need exchange slots below {self.hop_xslots}"
+            elif pairs and self._reach_over(x) is not None:
+                why = f"more than {self.hop_qmax} queues behind exchange-to-exchange bindings and alternate exchanges"
+            if why is not None:
+                del self.exchanges[key]
+                del self.exch_by_slot[slot]
+                self._free_x.append(slot)
+                raise ControlError(C.RESOURCE_ERROR, why, 40, 10)
         self._dlx_resolve(vhost, name)
         if _sync:
             self.routing_changed()
         return slot
+
+    @staticmethod
+    def check_alternate(arguments):
+        """The alternate-exchange argument of an Exchange.Declare as an exchange keeps it (None:
+        not given), or 406 PRECONDITION_FAILED: a string of at most 255 bytes."""
+        v = (arguments or {}).get("alternate-exchange")
+        if v is None:
+            return None
+        if isinstance(v, (bytes, bytearray)):
+            v = bytes(v).decode("utf-8", "surrogateescape")
+        if not isinstance(v, str) or len(v.encode("utf-8", "surrogateescape")) > 255:
+            raise ControlError(C.PRECONDITION_FAILED, f"invalid alternate-exchange {v!r}", 40, 10)
+        return v
+
+    def _alt_of(self, x):
+        """Exchange ``x``'s alternate exchange as it exists now (None: none named, no such
+        exchange, or the option off)."""
+        if not self.alternate_exchange or x.alt is None:
+            return None
+        return self.exchanges.get((x.vhost, x.alt))
 
     def _dlx_resolve(self, vhost, name):
         """Exchange ``name`` appeared or went: the queues that dead-letter to it look it up again."""
@@ -563,11 +616,15 @@ class ControlState:
         """The first exchange with outgoing edges whose key-blind reach (every exchange its
         edges lead to, whatever the key) binds more than hop_qmax distinct queues, or None.
         Only exchanges that reach ``changed`` (the exchange that just got a binding or an
-        edge) can have grown: its ancestors over the edges, and itself."""
+        edge) can have grown: its ancestors over the edges, and itself.  A resolved alternate
+        exchange is one more edge, here and in everything below."""
         preds = {}
         for x in self.exchanges.values():
             for b in x.xbindings + x.hxbindings:
                 preds.setdefault(b[0], set()).add(x.slot)
+            a = self._alt_of(x)
+            if a is not None:
+                preds.setdefault(a.slot, set()).add(x.slot)
         if not preds and not self._by_args(changed):
             return None
         up, todo = {changed.slot}, [changed.slot]
@@ -579,17 +636,24 @@ class ControlState:
         for slot in sorted(up):
             x = self.exch_by_slot[slot]
             # (a headers exchange matched on arguments is routed as a walk even without edges)
-            if not (x.xbindings or x.hxbindings or self._by_args(x)):
+            if not (x.xbindings or x.hxbindings or self._by_args(x) or self._alt_of(x) is not None):
                 continue
-            seen, todo, qs = {x.slot}, [x], set()
+            seen, todo, qs, dflt = {x.slot}, [x], set(), 0
             while todo:
                 cur = todo.pop()
+                if cur.name == "":
+                    # the default exchange (in a walk only as an alternate: it takes no edges) binds
+                    # every queue of its vhost by the queue's own name, so whatever the key it adds
+                    # one queue at most -- and declare_queue, which grows it, need not run this check
+                    dflt = 1
+                    continue
                 qs.update(b[0] for b in cur.bindings + cur.hbindings)
-                for s in [b[0] for b in cur.xbindings + cur.hxbindings]:
+                a = self._alt_of(cur)
+                for s in [b[0] for b in cur.xbindings + cur.hxbindings] + ([a.slot] if a is not None else []):
                     if s not in seen and s in self.exch_by_slot:
                         seen.add(s)
                         todo.append(self.exch_by_slot[s])
-            if len(qs) > self.hop_qmax:
+            if len(qs) + dflt > self.hop_qmax:
                 return x
         return None
 
@@ -683,7 +747,14 @@ class ControlState:
         exchange with the lowest slot is matched next, each exchange once (cycles end), and a
         queue is listed once, in discovery order.  ``route_flat(x, key)``: the queues of one
         exchange in its own list order (``route_flat(x, key, props)`` when the publish's
-        property bytes ``props`` are given: headers exchanges match on them)."""
+        property bytes ``props`` are given: headers exchanges match on them).
+
+        Alternate exchanges (alternate_exchange on; RabbitMQ's process_alternate): an exchange
+        whose own match gave no destination at all -- no queue and no edge, counted before the
+        walk's deduplication, so a queue listed earlier or an edge to a visited exchange is one --
+        and whose alternate exists makes that exchange pending unless it was visited; from there
+        it is a member of the walk like any other.  ``alt_taken`` counts the alternates taken this
+        way (one already visited is not taken: a cycle of alternates ends)."""
         if props:
             from ..models.matcher import props_headers
             props = props_headers(props)   # (read once for the whole walk)
@@ -696,12 +767,19 @@ class ControlState:
             pending.discard(s)
             visited.add(s)
             cur = self.exch_by_slot[s]
-            for q in flat(cur):
+            qs = flat(cur)
+            for q in qs:
                 if q not in seen:
                     seen.add(q)
                     out.append(q)
             edges = cur.hxbindings if self._by_args(cur) else cur.xbindings
-            pending.update(t for t in self._match_flat(cur, key, edges, props) if t not in visited)
+            ts = self._match_flat(cur, key, edges, props)
+            pending.update(t for t in ts if t not in visited)
+            if not qs and not ts:
+                a = self._alt_of(cur)
+                if a is not None and a.slot not in visited:
+                    self.alt_taken += 1
+                    pending.add(a.slot)
         return out
 
     def route_host(self, x, key, props=b""):
@@ -709,7 +787,7 @@ class ControlState:
         reaches through exchange ``x``, from the replicated binding table (what the device
         routes; headers routes as topic, SURVEY C27, or with headers-match on by its
         bindings' arguments).  Host-side routing for host-assembled large publishes."""
-        if x.xbindings or x.hxbindings:
+        if x.xbindings or x.hxbindings or self._alt_of(x) is not None:
             return self.route_closure(x, key, self._route_host_flat, props)
         return self._route_host_flat(x, key, props)
 

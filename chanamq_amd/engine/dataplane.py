@@ -72,8 +72,14 @@ class StepResult:
 class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
                  world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
-                 headers_match=False, queue_limits=False, dead_letter=False, x_death=False, **cfg):
-        """``x_death`` (needs ``dead_letter``): the dead pass rewrites each dead letter's property
+                 headers_match=False, queue_limits=False, dead_letter=False, x_death=False,
+                 alternate_exchange=False, **cfg):
+        """``alternate_exchange``: Exchange.Declare's alternate-exchange argument is honoured: an
+        exchange the walk of route_one matched without any destination hands the publish to the
+        exchange it names (x_alt; the ALT instantiations of k_route / k_import_route; n_alt).  Off:
+        the argument is ignored and the step launches the instantiations without the rule.
+
+        ``x_death`` (needs ``dead_letter``): the dead pass rewrites each dead letter's property
         bytes -- x-death / x-first-death-* headers, the expiration removed (k_dead_size,
         k_dead_pack<true>: dp_xdeath.h) -- and its routing refuses the queues the history bans
         (cycle detection; n_dl_cycle).  Off: the bytes are verbatim and the step's launches are
@@ -120,7 +126,8 @@ class GpuDataPlane(ControlState):
             full.setdefault("copy_engine", 3)
         full.update(device=device, hash_wildcard=int(hash_wildcard), graph=int(graph), world=world, rank=rank,
                     exchange_lag=int(exchange_lag), queue_limits=int(bool(queue_limits)),
-                    dead_letter=int(bool(dead_letter)), x_death=int(bool(x_death)))
+                    dead_letter=int(bool(dead_letter)), x_death=int(bool(x_death)),
+                    alternate_exchange=int(bool(alternate_exchange)))
         self.eng = self.mod.Engine(full)
         self.info = self.eng.info()
         sz = self.info["sizeof"]
@@ -176,7 +183,7 @@ class GpuDataPlane(ControlState):
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
                          shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits,
-                         dead_letter=dead_letter, x_death=x_death)
+                         dead_letter=dead_letter, x_death=x_death, alternate_exchange=alternate_exchange)
 
     # ================================================================== uploads
     # ``defer`` (set by the broker around control work done while steps keep running): table
@@ -222,6 +229,7 @@ class GpuDataPlane(ControlState):
         x_hkey = np.zeros(xh, np.uint64)
         x_hval = np.full(xh, -1, np.int32)
         x_type = np.zeros(self.x_max, np.uint32)
+        x_alt = np.full(self.x_max, -1, np.int32)   # the alternate exchange's slot as it exists now
         x_fan_off = np.zeros(self.x_max, np.uint32)
         x_fan_n = np.zeros(self.x_max, np.uint32)
         x_t_off = np.zeros(self.x_max, np.uint32)
@@ -257,6 +265,11 @@ class GpuDataPlane(ControlState):
             else:
                 raise ControlError(C.RESOURCE_ERROR, "exchange hash full")
             x_type[x.slot] = C.EXCHANGE_TYPE_ID[x.type] | (0x100 if x.xbindings or x.hxbindings else 0)
+            alt = self._alt_of(x)
+            if alt is not None:
+                # XF_HOP: a publish that enters here is routed as a walk, which may take the alternate
+                x_alt[x.slot] = alt.slot
+                x_type[x.slot] |= 0x100
             if self._by_args(x):
                 # XF_HMATCH, and always XF_HOP: its publishes are routed as a walk, edges or none
                 # (the queue list goes through hop_q to pass 1, which then never matches again)
@@ -354,6 +367,8 @@ class GpuDataPlane(ControlState):
                           ("t_count", np.array([len(tb), 0, 0, 0], np.uint32)),
                           ("x_h_off", x_h_off), ("x_h_n", x_h_n)):
             self._up_diff(name, arr)
+        if self.alternate_exchange:
+            self._up_diff("x_alt", x_alt)
         if hrows:
             self._up_diff("h_queue", h_rows[:, 0])
             self._up_diff("h_meta", h_rows[:, 1])

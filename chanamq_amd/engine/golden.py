@@ -282,7 +282,10 @@ class GoldenDataPlane(ControlState):
                 continue
             rk = m.rk if it["rk"] is None else it["rk"]
             x = self.exch_by_slot.get(it["xs"])
+            alt0 = self.alt_taken
             qs = self._route(x, rk, it["props"]) if x is not None else []
+            if self.alternate_exchange:
+                cnt["n_alt"] += self.alt_taken - alt0
             if it["bans"]:   # cycle detection: a banned queue is refused, the others still get it
                 cnt["n_dl_cycle"] += sum(1 for q in qs if q in it["bans"])
                 qs = [q for q in qs if q not in it["bans"]]
@@ -859,7 +862,10 @@ class GoldenDataPlane(ControlState):
             cnt["n_unknown_exchange"] += 1
             out["events"].append((conn, 404, s))
             return
+        alt0 = self.alt_taken
         qs = self._route(x, rk, props)
+        if self.alternate_exchange:   # (the origin's walk; the owner's re-match is not counted again)
+            cnt["n_alt"] += self.alt_taken - alt0
         remote = sorted({self.queue_by_slot[q].owner for q in qs} - {self.rank}) if self.world > 1 else []
         ret = 0
         if not qs:
@@ -932,7 +938,9 @@ class GoldenDataPlane(ControlState):
             ring.append((msg, False, e))
 
     def _route(self, x, rk, props=b""):
-        if x.xbindings or x.hxbindings:   # exchange-to-exchange edges: the closure, each exchange matched once
+        # exchange-to-exchange edges, or an alternate exchange that may be taken: the closure, each
+        # exchange matched once
+        if x.xbindings or x.hxbindings or self._alt_of(x) is not None:
             return self.route_closure(x, rk, self._route_flat, props)
         return self._route_flat(x, rk, props)
 

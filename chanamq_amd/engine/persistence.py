@@ -316,6 +316,13 @@ class GpuPersistence:
             v, name = _split_eid(xid)
             v = v or "AMQ.DEFAULT"
             p.ensure_vhost(v)
+            # (alternate exchanges: a declare that creates or resolves an alternate pair is held to the
+            # walk's limits.  Reach only grows as exchanges and bindings are added, so a store whose
+            # final topology passed the reach check is never refused for it part-way through,
+            # whatever the order of its exchanges -- and here no queue is bound yet.  The slot bound
+            # does depend on the order: slots are handed out as the exchanges are declared, so with
+            # more than hop_xslots exchanges (x_max above 2048) one of a pair that sat below the
+            # bound live may be given a slot at or above it here, and that declare is refused)
             p.declare_exchange(v, name, tpe, durable=durable, auto_delete=autodel, internal=internal,
                                arguments=args)
             binds += [(v, _split_eid(qid)[1], name, key, dict(a or {})) for qid, key, a in bl]

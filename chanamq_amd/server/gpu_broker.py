@@ -220,7 +220,7 @@ class GpuBroker:
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
                  persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False,
-                 dead_letter=False, x_death=False):
+                 dead_letter=False, x_death=False, alternate_exchange=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -257,6 +257,12 @@ class GpuBroker:
             raise ValueError("x_death=True needs dead_letter=True")
         if self.x_death and not getattr(plane, "x_death", False):
             raise ValueError("x_death=True needs a data plane built with x_death=True")
+        # alternate exchanges (chana.mq.gpu.alternate-exchange): the plane's work (built with
+        # alternate_exchange=True: Exchange.Declare's argument is validated, kept and routed by);
+        # here the alt_routed statistic, and the argument's check in front of a sharded declare
+        self.alternate_exchange = bool(alternate_exchange)
+        if self.alternate_exchange and not getattr(plane, "alternate_exchange", False):
+            raise ValueError("alternate_exchange=True needs a data plane built with alternate_exchange=True")
         native_x = bool(getattr(plane, "native_xchg", False))
         if io == "auto":
             io = "pipeline" if (hasattr(plane, "eng") and (node is None or native_x)) else "native"
@@ -371,6 +377,8 @@ class GpuBroker:
             self.stats.update(dict.fromkeys(self.DL_STATS, 0))
         if self.x_death:
             self.stats["dl_cycle"] = 0
+        if self.alternate_exchange:
+            self.stats["alt_routed"] = 0
         self.lock = _PlaneLock(self)
         self.light = _LightLock(self.lock)
 
@@ -836,6 +844,8 @@ class GpuBroker:
             self.stats.update({k: st.get(k, 0) for k in self.DL_STATS})
         if self.x_death:
             self.stats["dl_cycle"] = st.get("dl_cycle", 0)
+        if self.alternate_exchange:
+            self.stats["alt_routed"] = st.get("alt_routed", 0)
         if st.get("spill_moved"):
             self.stats["spilled_bytes"] = st["spill_moved"]
         self._fe_stats = st
@@ -1267,6 +1277,8 @@ class GpuBroker:
             self.stats["dl_pending"] = cnt.get("n_dl_pending", 0)
         if self.x_death:   # (dead letter, queue) pairs refused: the queue is in the dead letter's own history
             self.stats["dl_cycle"] += cnt.get("n_dl_cycle", 0)
+        if self.alternate_exchange:   # (publish, exchange) pairs whose alternate exchange was taken
+            self.stats["alt_routed"] += cnt.get("n_alt", 0)
         for conn, code, chslot in events:
             c = self.conns.get(conn)
             if c is None or c.state != "open":
@@ -1856,6 +1868,11 @@ class GpuBroker:
                 raise ControlError(C.ACCESS_REFUSED, f"exchange name '{m.exchange}' is reserved", 40, 10)
             if x is not None and x.type != m.type:
                 raise ControlError(C.PRECONDITION_FAILED, f"exchange '{m.exchange}' declared as {x.type}", 40, 10)
+            if p.alternate_exchange:   # (406 before anything is submitted; every replica applies the rule)
+                alt = p.check_alternate(m.arguments)
+                if x is not None and alt is not None and x.alt != alt:
+                    raise ControlError(C.PRECONDITION_FAILED, f"exchange '{m.exchange}' is declared with "
+                                       f"alternate-exchange {x.alt!r}", 40, 10)
             seq = node.submit("declare_exchange", vh, m.exchange, m.type or "direct", durable=m.durable,
                               auto_delete=m.auto_delete, internal=m.internal, arguments=dict(m.arguments or {}))
             reply = None if m.nowait else (lambda r: Method("exchange.declare_ok"))

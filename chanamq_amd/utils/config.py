@@ -302,6 +302,10 @@ class Config:
             if not dead_letter:
                 raise ValueError("chana.mq.gpu.dead-letter-x-death needs chana.mq.gpu.dead-letter")
             plane.update(x_death=True)
+        # Exchange.Declare's alternate-exchange is honoured (off: the argument is ignored)
+        alternate_exchange = bool(g(k + "alternate-exchange", False))
+        if alternate_exchange:
+            plane.update(alternate_exchange=True)
         hi = int(g("chana.mq.flow.memory-high-watermark", -1))
         lo = int(g("chana.mq.flow.memory-low-watermark", -1))
         if hi < 0:   # 40% of what the broker can hold: the HBM body log + the host spill ring
@@ -314,6 +318,7 @@ class Config:
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
                       headers_match=headers_match, queue_limits=queue_limits, dead_letter=dead_letter, x_death=x_death,
+                      alternate_exchange=alternate_exchange,
                       mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 

@@ -325,6 +325,7 @@ PYBIND11_MODULE(_core, m) {
              o["maxlen_dropped"] = s.maxlen_dropped; o["maxlen_rejected"] = s.maxlen_rejected;
              o["dl_expired"] = s.dl_expired; o["dl_maxlen"] = s.dl_maxlen; o["dl_rejected"] = s.dl_rejected;
              o["dl_unrouted"] = s.dl_unrouted; o["dl_dropped"] = s.dl_dropped; o["dl_pending"] = s.dl_pending; o["dl_cycle"] = s.dl_cycle;
+             o["alt_routed"] = s.alt_routed;
              o["wait_s"] = s.wait_s;
              o["submit_s"] = s.submit_s;
              o["xchg_s"] = s.xchg_s; o["xchg_steps"] = s.xchg_steps; o["syncs"] = s.syncs;

@@ -1309,6 +1309,7 @@ void Frontend::finish_oldest(std::deque<Inflight>& inflight) {
     stats_.dl_dropped += c.n_dl_dropped;
     stats_.dl_pending = c.n_dl_pending;
     stats_.dl_cycle += c.n_dl_cycle;
+    stats_.alt_routed += c.n_alt;
     stats_.ctrl += c.n_ctrl;
     stats_.live_msgs = c.n_live_msgs;
     stats_.log_used = c.log_head - c.log_tail;

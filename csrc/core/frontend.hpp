@@ -111,6 +111,7 @@ struct FeStats {
   u64 maxlen_dropped = 0, maxlen_rejected = 0;   // x-max-length: trimmed from queue heads / publishes refused
   // dead-lettering: entries dead-lettered by reason, dead letters lost, entries pending (a gauge)
   u64 dl_expired = 0, dl_maxlen = 0, dl_rejected = 0, dl_unrouted = 0, dl_dropped = 0, dl_pending = 0, dl_cycle = 0;
+  u64 alt_routed = 0;   // alternate exchanges: (publish, exchange) pairs whose alternate was taken
   i64 live_bytes = 0;
   u64 live_msgs = 0;
   u64 log_used = 0;          // body-log occupancy (head - tail): the oldest live message pins it

@@ -1140,6 +1140,15 @@ struct HopWalk {
   u32 visited = 0, pending = 0;
 };
 
+// the walk of an ALT instantiation (alternate exchanges): whether the exchange being matched had a
+// destination of its own -- wave-uniform, taken from values the matchers hold anyway (a list's
+// length, the last hit) -- and the alternates the walk has taken.  A type of its own, so that the
+// other instantiations' walk, and with it their code, is what it was
+struct HopWalkAlt : HopWalk {
+  bool dest = false;
+  u32 nalt = 0;
+};
+
 // one candidate per lane: a queue (appended unless listed) or XT_EDGE | destination exchange
 DEV void hop_add(HopWalk& h, u32 item, bool valid, u32 lane) {
   const bool isx = valid && (item & XT_EDGE);
@@ -1212,7 +1221,12 @@ DEV void hop_finish(const DS& d, RouteAcc<0>& a, const HopWalk& h, const Pub& pb
   if (lane == 0) d.pub_qc[(u64)p * PUB_QC] = XT_EDGE | off;
 }
 
-template <int PASS, bool BAN = false>
+// ALT (alternate exchanges, pass 0 with the option on): an exchange the walk matched without any
+// destination -- no queue and no edge hit, counted before the walk's list and its visited set
+// drop what they hold already, and before BAN refuses a queue -- hands the publish to the
+// exchange x_alt names, one more pending member of the walk (the rule: control.py route_closure).
+// The host gives an exchange with an alternate XF_HOP, so its publishes are walked
+template <int PASS, bool BAN = false, bool ALT = false>
 DEV void route_one(const DS& d, u32 p, u32 lane) {
   Pub& pb = d.pubs[p];
   // pass 0 of an imported record that arrived with its queue ran in import_one
@@ -1250,7 +1264,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
     // a walk over exchange-to-exchange edges (pass 0; pass 1 was served from pub_qc / hop_q
     // above): the loop below runs once per visited exchange, candidates go to the walk's list
     const bool hop = PASS == 0 && __builtin_expect((xt & XF_HOP) != 0, 0);
-    HopWalk h;
+    std::conditional_t<ALT, HopWalkAlt, HopWalk> h;
     u32 x = (u32)ex;
     if (hop) {
       __shared__ u32 hop_list[16][HOP_QMAX];   // (route pass 0 runs at most 16 waves per block)
@@ -1287,6 +1301,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
             const bool v = k0 + lane < xc;
             hop_add(h, v ? (xl[xo + k0 + lane] | XT_EDGE) : 0u, v, lane);
           }
+          if constexpr (ALT) h.dest = c + xc != 0;
         }
       } else if (PASS == 0 && __builtin_expect(hop && (xt & XF_HMATCH) != 0, 0)) {
         // headers, matched on the bindings' arguments against the publish's own property bytes
@@ -1314,6 +1329,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
             hop_add(h, q, hit && (below ? qb : lastq) != q, lane);
             if (hm) lastq = qtop;
           }
+          if constexpr (ALT) h.dest = lastq != INVALID;   // (a hit row's queue or edge word is never INVALID)
         }
       } else {
         u32 o = d.x_t_off[x], c = d.x_t_n[x];
@@ -1344,12 +1360,32 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
           else route_emit<PASS, BAN>(d, a, p, wbase, srank, q, emit, lane, qo, qc);
           if (hm) lastq = qtop;
         }
+        if constexpr (ALT) h.dest = lastq != INVALID;
+      }
+      if constexpr (ALT && PASS == 0) {
+        if (hop && !h.dest) {
+          // taken (and counted) unless it was visited already; the host keeps both slots below HOP_XSLOTS
+          const i32 al = d.x_alt[x];
+          if (al >= 0 && (u32)al < HOP_XSLOTS) {
+            const u32 vis = (u32)__shfl((int)h.visited, al >> 5);
+            if (!((vis >> (al & 31)) & 1)) {
+              hop_add(h, (u32)al | XT_EDGE, lane == 0, lane);
+              ++h.nalt;
+            }
+          }
+        }
       }
       if (__builtin_expect(!hop, 1) || !hop_next(h, x, lane)) break;
       xt = d.x_type[x] & (XF_TYPE | XF_HMATCH);
     }
     if constexpr (PASS == 0) {
       if (hop) hop_finish<BAN>(d, a, h, pb, p, srank, lane);
+    }
+    if constexpr (ALT && PASS == 0) {
+      // lane 0 adds the walk's count once.  Counted by the walk of the publish's own rank: an owner's
+      // re-match of a record follows the same alternates without counting them again (the dead
+      // pass's records are world 1's)
+      if (hop && lane == 0 && h.nalt && (d.world == 1 || !(pb.flags & MF_IMPORTED))) atomicAdd(&d.ctr->n_alt, h.nalt);
     }
   }
   if (PASS == 0 && lane == 0) {
@@ -1403,12 +1439,12 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
 
 // routing pass 0 of the group of 16 publishes [g0, g0 + 16) below n by a 1024-thread block:
 // the group's topic prefilter tiles, then wave w routes publish g0 + w
-template <bool BAN = false>
+template <bool BAN = false, bool ALT = false>
 DEV void route_group(const DS& d, u32 g0, u32 n, u32 w, u32 lane) {
   topic_group(d, g0, n, w, lane);
   __threadfence_block();
   __syncthreads();
-  if (g0 + w < n) route_one<0, BAN>(d, g0 + w, lane);
+  if (g0 + w < n) route_one<0, BAN, ALT>(d, g0 + w, lane);
   __syncthreads();   // the next group's tiles overwrite nothing this group reads, but keep waves together
 }
 
@@ -1419,6 +1455,7 @@ DEV void route_group(const DS& d, u32 g0, u32 n, u32 w, u32 lane) {
 #ifndef ROUTE_WPE   // k_route occupancy target: 8 (two blocks per CU, 64 VGPRs, 12 VGPRs spilled)
 #define ROUTE_WPE 8     // or 4 (one block per CU, no spill): A/B through CHANAMQ_DP_SO
 #endif
+template <bool ALT>   // (with alternate exchanges on: route_one's rule for an exchange without a destination)
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(ROUTE_WPE))) void k_route(DS d) {
   // the wave index as a scalar: each wave's publish index, and every pointer derived from
   // it, then lives in SGPRs (as a VGPR value it pushed the wave router past 64 VGPRs and
@@ -1431,7 +1468,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(ROUTE_WPE)
   // for capacity (2048 blocks), and the register allocator spills loop-invariant state to
   // scratch in the prologue -- 1 KB of HBM writes per idle wave otherwise (PMC WRITE_SIZE)
   if (lo + blockIdx.x * 16 >= n) return;
-  for (u32 g0 = lo + blockIdx.x * 16; g0 < n; g0 += gridDim.x * 16) route_group(d, g0, n, w, lane);
+  for (u32 g0 = lo + blockIdx.x * 16; g0 < n; g0 += gridDim.x * 16) route_group<false, ALT>(d, g0, n, w, lane);
 }
 
 // reserve the step's contiguous body-log region and message-table indices
@@ -1781,7 +1818,8 @@ DEV void pack_one(const DS& d, u32 p, u32 lane, const u32* s_base) {
 // at once)
 DEV void import_one(const DS& d, u32 i, const u32* xr);
 DEV void link_ack_one(const DS& d, u32 i);
-template <bool BAN>   // (the dead view's launch with x-death on: route_emit's ban check)
+// (BAN: the dead view's launch with x-death on, route_emit's ban check; ALT: with alternate exchanges on)
+template <bool BAN, bool ALT = false>
 __global__ __launch_bounds__(1024) void k_import_route(DS d) {
   __shared__ u32 xr[4 * WORLD_MAX];
   __shared__ u32 s_n, s_k;
@@ -1826,7 +1864,7 @@ __global__ __launch_bounds__(1024) void k_import_route(DS d) {
     if (tid < 16 && g0 + tid < n) import_one(d, g0 + tid, xr);
     __threadfence_block();
     __syncthreads();
-    route_group<BAN>(d, base + g0, base + n, w, lane);
+    route_group<BAN, ALT>(d, base + g0, base + n, w, lane);
   }
 }
 

@@ -378,6 +378,10 @@ struct DS {
   u32 dlx;                  // kernel-uniform, like limits: 1 on; 2 in the DS view of the dead pass
   const DlState* dl;        // device: the feature's tables and buffers (one pointer here: DS is the argument
                             // of every kernel of every step, the flag on or off)
+
+  // ---------------- alternate exchanges (alternate-exchange): read only by the ALT instantiations of
+  // routing pass 0, which the engine launches with the option on
+  i32* x_alt;               // [x_max] slot of the exchange's alternate exchange as it exists now, or -1
 };
 struct DlState {
   u32 dead_max;             // items of the dead list (<= DEAD_LIST_MAX)

@@ -206,6 +206,7 @@ class Engine {
     // at most import_max of them a step
     if (get("x_death", 0) && !get("dead_letter", 0)) throw std::runtime_error("x_death needs dead_letter");
     d_.dlx = get("dead_letter", 0) ? 1u : 0u;
+    alt_ = get("alternate_exchange", 0) != 0;
     if (d_.dlx) {
       if (d_.world != 1)
         throw std::runtime_error("dead_letter: single-rank planes only (a dead-letter exchange's queues may live on "
@@ -482,6 +483,8 @@ class Engine {
     d_.t_woff = (u16*)dev("t_woff", 2ull * TOPIC_WORDS * d_.tb_pad + 64);
     d_.x_h_off = (u32*)dev("x_h_off", 4ull * d_.x_max);
     d_.x_h_n = (u32*)dev("x_h_n", 4ull * d_.x_max);
+    d_.x_alt = (i32*)dev("x_alt", 4ull * d_.x_max);
+    HIPCHECK(hipMemset(d_.x_alt, 0xff, 4ull * d_.x_max));   // (until the first topology upload: no alternates)
     d_.h_queue = (u32*)dev("h_queue", 4ull * hb_max_);
     d_.h_meta = (u32*)dev("h_meta", 4ull * hb_max_);
     d_.h_pair = (u32*)dev("h_pair", 4ull * hb_max_);
@@ -1012,6 +1015,7 @@ class Engine {
     o["h2d_split_min"] = h2d_split_min_;
     o["queue_limits"] = d_.limits;
     o["dead_letter"] = d_.dlx; o["dead_max"] = dl_h_.dead_max; o["dead_bytes"] = dl_h_.dead_bytes; o["dead_room"] = dead_room_; o["x_death"] = dl_h_.xdeath;
+    o["alternate_exchange"] = alt_ ? 1 : 0;
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
     o["restore_max"] = restore_max_;
     o["xfer_desc_max"] = d_.xfer_desc_max; o["xfer_bytes"] = d_.xfer_bytes; o["world_max"] = WORLD_MAX;
@@ -1037,6 +1041,7 @@ class Engine {
   bool lag_ = false, native_x_ = false, links_ = false;
   u32 restore_max_ = 0;
   u32 dead_room_ = 0;      // records one dead pass takes: min(import_max, dead_max)
+  bool alt_ = false;       // alternate exchanges (cfg alternate_exchange): routing pass 0 runs its ALT instantiations
   DlState dl_h_{};         // host copy of DS.dl
   u64 carry_budget_ = 0;
   int copy_mode_ = 0;      // cfg copy_engine
@@ -1613,6 +1618,7 @@ class Engine {
     // string and a hash on the host's per-step path, which the headline benchmark drives)
     if (d_.dlx) { F(n_dl_expired); F(n_dl_maxlen); F(n_dl_rejected); F(n_dl_unrouted); F(n_dl_dropped); F(n_dl_pending); }
     if (dl_h_.xdeath) F(n_dl_cycle);
+    if (alt_) F(n_alt);
 #undef F
     std::vector<u32> lat(c.lat_hist, c.lat_hist + LAT_BINS);
     o["lat_hist"] = lat;
@@ -2742,9 +2748,13 @@ class Engine {
     // (k_route: 2 per CU at 64 VGPRs; k_import_route: 1), not the capacity's groups --
     // the idle blocks of a capacity-sized grid were still dispatched after the busy ones
     const u64 ngroups = ceil_div(nmax ? nmax : 1, 16);
-    if (imports && ban) hipLaunchKernelGGL(k_import_route<true>, capped(ngroups, n_cu_), dim3(1024), 0, s, d);
+    // (alt_: the instantiations with the alternate-exchange rule, launched only with the option on)
+    if (imports && ban && alt_) hipLaunchKernelGGL((k_import_route<true, true>), capped(ngroups, n_cu_), dim3(1024), 0, s, d);
+    else if (imports && ban) hipLaunchKernelGGL(k_import_route<true>, capped(ngroups, n_cu_), dim3(1024), 0, s, d);
+    else if (imports && alt_) hipLaunchKernelGGL((k_import_route<false, true>), capped(ngroups, n_cu_), dim3(1024), 0, s, d);
     else if (imports) hipLaunchKernelGGL(k_import_route<false>, capped(ngroups, n_cu_), dim3(1024), 0, s, d);   // + prep, link acks
-    else hipLaunchKernelGGL(k_route, capped(ngroups, 2 * n_cu_), dim3(1024), 0, s, d);
+    else if (alt_) hipLaunchKernelGGL(k_route<true>, capped(ngroups, 2 * n_cu_), dim3(1024), 0, s, d);
+    else hipLaunchKernelGGL(k_route<false>, capped(ngroups, 2 * n_cu_), dim3(1024), 0, s, d);
     // scan of the routing counts + the phase's log reservation, then pairs + store
     const ScanArgs a = scan_args({{d.pub_nq, d.pub_pair_off}, {d.pub_slot, d.pub_slot_off},
                                   {d.pub_routed, d.pub_routed_rank}, {d.pub_ret_sz, d.pub_ret_off}},

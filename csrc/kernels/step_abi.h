@@ -83,6 +83,9 @@ struct Counters {       // per-step counters (device -> host)
   // x-death (DlState.xdeath): (dead letter, queue) pairs the dead pass's routing refused because
   // the dead letter's history bans the queue (a cycle without a reject in it)
   u32 n_dl_cycle, dl_pad;
+  // alternate exchanges: (publish, exchange) pairs of the step whose exchange matched no
+  // destination and handed the publish to its alternate exchange (route_one's walk)
+  u32 n_alt, alt_pad;
   u64 log_head, log_tail;
   u32 msg_free_top, n_live_msgs;
   i64 live_bytes;       // body-log slot bytes of live messages (exact, unlike head - tail)
@@ -135,7 +138,7 @@ struct DeltaRec { u64 dst; u32 len; u32 chunk0; };
 // C entry points of one Engine (engine.hip: Engine::c_api).  All return 0 / a parity on
 // success and -1 on error (message: error()).  Parity p = the double-buffered step IO set
 // of a submitted step; its host-mapped outputs stay valid until the next submit of p.
-#define CMQ_STEP_ABI 11
+#define CMQ_STEP_ABI 12
 #define PSLOTS 4                // rotating host store-record slots (a step's records live PSLOTS - 1 more steps)
 #define UNPAUSE_STEP_MAX 1024   // connections unpaused per step (StepIn.nunp)
 struct CmqEngineApi {
