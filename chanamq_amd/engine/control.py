@@ -71,6 +71,9 @@ class Queue:
     # limit); "drop-head" trims the head at the end of a step, "reject-publish" refuses at enqueue
     max_length: Optional[int] = None
     overflow: str = "drop-head"
+    # x-max-length-bytes (queue_limit_bytes on): at most this many ready body bytes (None: no
+    # limit), under the same overflow mode
+    max_length_bytes: Optional[int] = None
     # x-dead-letter-exchange / x-dead-letter-routing-key (dead_letter on): the exchange's name, looked
     # up in the queue's vhost when a message dies (it need not exist), and the key its dead
     # letters are published with (None: each message's own)
@@ -138,7 +141,12 @@ class ControlState:
     def __init__(self, c_max=1024, chpc=16, q_max=4096, x_max=1024, cons_max=16384,
                  hash_wildcard=True, ring_pool=1 << 26, default_queue_capacity=1 << 16,
                  world=1, rank=0, shard_map=None, headers_match=False, queue_limits=False, dead_letter=False, x_death=False,
-                 alternate_exchange=False):
+                 alternate_exchange=False, queue_limit_bytes=False):
+        # chana.mq.gpu.queue-limit-bytes: a queue's x-max-length-bytes is honoured, under its
+        # x-overflow mode (off: it is ignored).  The mode is the count limit's, so it needs queue_limits
+        self.queue_limit_bytes = bool(queue_limit_bytes)
+        if self.queue_limit_bytes and not queue_limits:
+            raise ValueError("queue_limit_bytes=True needs queue_limits=True")
         # chana.mq.gpu.alternate-exchange: Exchange.Declare's alternate-exchange argument is honoured
         # -- an exchange the walk matched without any destination hands the publish to the exchange
         # it names (route_closure has the rule; off: the argument is ignored, as the reference does)
@@ -375,7 +383,7 @@ class ControlState:
 
     def declare_queue(self, vhost, name, durable=False, exclusive_owner=-1, auto_delete=False,
                       ttl_ms=0, capacity=None, passive=False, max_capacity=0, max_length=None, overflow="drop-head",
-                      dead_letter_exchange=None, dead_letter_routing_key=None):
+                      dead_letter_exchange=None, dead_letter_routing_key=None, max_length_bytes=None):
         key = (vhost, name)
         q = self.queues.get(key)
         if not self.dead_letter:
@@ -386,6 +394,10 @@ class ControlState:
             max_length = None
         elif max_length is not None:
             max_length, overflow = self.check_limit(max_length, overflow)
+        if not self.queue_limit_bytes:
+            max_length_bytes = None
+        elif max_length_bytes is not None:
+            max_length_bytes, overflow = self.check_limit_bytes(max_length_bytes, overflow)
         if q is not None:
             # a declare of an existing queue returns its slot; with queue_limits on, a limit that
             # differs from the queue's is refused, but a queue without one (a recovered durable
@@ -394,13 +406,29 @@ class ControlState:
             if dlx is not None and not passive and q.dlx is not None and (q.dlx, q.dlk) != (dlx, dlk):
                 raise ControlError(C.PRECONDITION_FAILED, f"queue '{name}' is declared with "
                                    f"x-dead-letter-exchange '{q.dlx}'", 50, 10)
-            if max_length is not None and not passive:
-                if q.max_length is None:
-                    q.max_length, q.overflow = max_length, overflow
-                    self.queue_limit_changed(q)
-                elif (q.max_length, q.overflow) != (max_length, overflow):
+            # (the byte limit by the same rule; the two share the mode, so a declare that carries
+            # either must name the mode of a queue that has either; every check before any change)
+            if (max_length is not None or max_length_bytes is not None) and not passive:
+                limited = q.max_length is not None or q.max_length_bytes is not None
+                if max_length is not None and q.max_length is not None and \
+                        (q.max_length, q.overflow) != (max_length, overflow):
                     raise ControlError(C.PRECONDITION_FAILED, f"queue '{name}' is declared with x-max-length "
                                        f"{q.max_length} ({q.overflow})", 50, 10)
+                if max_length_bytes is not None and q.max_length_bytes is not None and \
+                        (q.max_length_bytes, q.overflow) != (max_length_bytes, overflow):
+                    raise ControlError(C.PRECONDITION_FAILED, f"queue '{name}' is declared with x-max-length-bytes "
+                                       f"{q.max_length_bytes} ({q.overflow})", 50, 10)
+                if limited and q.overflow != overflow:
+                    raise ControlError(C.PRECONDITION_FAILED, f"queue '{name}' is declared with x-overflow "
+                                       f"{q.overflow}", 50, 10)
+                if (max_length is not None and q.max_length is None) or \
+                        (max_length_bytes is not None and q.max_length_bytes is None):
+                    if q.max_length is None:
+                        q.max_length = max_length
+                    if q.max_length_bytes is None:
+                        q.max_length_bytes = max_length_bytes
+                    q.overflow = overflow
+                    self.queue_limit_changed(q)
             # the dead-letter pair by the same rule (it is not stored either)
             if dlx is not None and not passive and q.dlx is None:
                 q.dlx, q.dlk = dlx, dlk
@@ -418,8 +446,9 @@ class ControlState:
         slot = self._free_q.pop()
         q = Queue(slot, vhost, name, durable, exclusive_owner, auto_delete, ttl_ms, cap,
                   self._ring_alloc(cap), owner=owner, requested=capacity, max_capacity=max_capacity,
-                  max_length=max_length, overflow=overflow if max_length is not None else "drop-head",
-                  dlx=dlx, dlk=dlk)
+                  max_length=max_length,
+                  overflow=overflow if (max_length is not None or max_length_bytes is not None) else "drop-head",
+                  dlx=dlx, dlk=dlk, max_length_bytes=max_length_bytes)
         self.queues[key] = q
         self.queue_by_slot[slot] = q
         dx = self.exchanges.get((vhost, ""))
@@ -462,11 +491,27 @@ class ControlState:
             raise ControlError(C.PRECONDITION_FAILED, f"invalid x-overflow {overflow!r}", 50, 10)
         return min(max_length, cls.MAX_LENGTH_TOP), overflow
 
-    def set_queue_limit(self, slot, max_length, overflow="drop-head"):
-        """Queue ``slot``'s limit as given (None: none), on this plane only: a reload lifts the
-        limit while it restores the queue's messages and puts it back afterwards."""
+    @classmethod
+    def check_limit_bytes(cls, max_length_bytes, overflow="drop-head"):
+        """(max_length_bytes, overflow) as a queue keeps them, or 406 PRECONDITION_FAILED: the bytes
+        an integer >= 0 (kept in 64 bits), the mode one of the two served."""
+        v = max_length_bytes
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ControlError(C.PRECONDITION_FAILED, f"invalid x-max-length-bytes {v!r}", 50, 10)
+        if overflow is None:
+            overflow = "drop-head"
+        if overflow not in cls.OVERFLOW_MODES:
+            raise ControlError(C.PRECONDITION_FAILED, f"invalid x-overflow {overflow!r}", 50, 10)
+        return min(v, cls.MAX_LENGTH_BYTES_TOP), overflow
+
+    MAX_LENGTH_BYTES_TOP = (1 << 63) - 2   # (q_blimit holds B + 1 in 64 bits)
+
+    def set_queue_limit(self, slot, max_length, overflow="drop-head", max_length_bytes=None):
+        """Queue ``slot``'s limits as given (None: none), on this plane only: a reload lifts them
+        while it restores the queue's messages and puts them back afterwards."""
         q = self.queue_by_slot[slot]
-        q.max_length, q.overflow = max_length, (overflow if max_length is not None else "drop-head")
+        q.max_length, q.max_length_bytes = max_length, max_length_bytes
+        q.overflow = overflow if (max_length is not None or max_length_bytes is not None) else "drop-head"
         self.queue_limit_changed(q)
 
     def grow_target(self, q, depth):

@@ -73,8 +73,14 @@ class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
                  world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
                  headers_match=False, queue_limits=False, dead_letter=False, x_death=False,
-                 alternate_exchange=False, **cfg):
-        """``alternate_exchange``: Exchange.Declare's alternate-exchange argument is honoured: an
+                 alternate_exchange=False, queue_limit_bytes=False, **cfg):
+        """``queue_limit_bytes`` (needs ``queue_limits``): queues honour x-max-length-bytes under
+        their x-overflow mode (q_blimit; the device keeps every queue's ready bytes in q_bytes:
+        k_byte_room and the BL instantiations of k_ring_plan / k_enqueue / k_dequeue / k_basic_get;
+        the step sorts its pairs on the materialised path at every key width).  Off: the argument
+        is ignored and the step launches what it launched before.
+
+        ``alternate_exchange``: Exchange.Declare's alternate-exchange argument is honoured: an
         exchange the walk of route_one matched without any destination hands the publish to the
         exchange it names (x_alt; the ALT instantiations of k_route / k_import_route; n_alt).  Off:
         the argument is ignored and the step launches the instantiations without the rule.
@@ -108,6 +114,8 @@ class GpuDataPlane(ControlState):
             raise ValueError("dead_letter=True is not served on a sharded plane (world > 1)")
         if x_death and not dead_letter:
             raise ValueError("x_death=True needs dead_letter=True")
+        if queue_limit_bytes and not queue_limits:
+            raise ValueError("queue_limit_bytes=True needs queue_limits=True")
         self.mod = ops.load()
         full = dict(cfg)
         full.setdefault("egress_ref_back", -1 if egress_ref is None else int(egress_ref))
@@ -128,6 +136,8 @@ class GpuDataPlane(ControlState):
                     exchange_lag=int(exchange_lag), queue_limits=int(bool(queue_limits)),
                     dead_letter=int(bool(dead_letter)), x_death=int(bool(x_death)),
                     alternate_exchange=int(bool(alternate_exchange)))
+        if queue_limit_bytes:   # (off: the engine's cfg is what it was)
+            full.update(queue_limit_bytes=1)
         self.eng = self.mod.Engine(full)
         self.info = self.eng.info()
         sz = self.info["sizeof"]
@@ -183,7 +193,8 @@ class GpuDataPlane(ControlState):
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
                          shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits,
-                         dead_letter=dead_letter, x_death=x_death, alternate_exchange=alternate_exchange)
+                         dead_letter=dead_letter, x_death=x_death, alternate_exchange=alternate_exchange,
+                         queue_limit_bytes=queue_limit_bytes)
 
     # ================================================================== uploads
     # ``defer`` (set by the broker around control work done while steps keep running): table
@@ -494,6 +505,8 @@ class GpuDataPlane(ControlState):
         self._up_at("q_head", 0, q.slot, np.uint64)
         self._up_at("q_tail", 0, q.slot, np.uint64)
         self._up_at("q_ttl", q.ttl_ms, q.slot, np.int64)
+        if self.queue_limit_bytes:   # (an empty ring holds no bytes: zeroed with the head)
+            self._up_at("q_bytes", 0, q.slot, np.uint64)
         if self.queue_limits:
             self.queue_limit_changed(q)
         if self.dead_letter:
@@ -506,10 +519,18 @@ class GpuDataPlane(ControlState):
     def queue_limit_changed(self, q):
         # q_limit (dp_state.h): 0 = no limit, else (L + 1) | QL_REJECT; a queue owned by another
         # rank holds nothing here (its owner enforces the limit)
-        ql = 0
-        if q.max_length is not None and q.owner == self.rank:
-            ql = (min(int(q.max_length), self.MAX_LENGTH_TOP) + 1) | (0x80000000 if q.overflow == "reject-publish" else 0)
+        # q_blimit (queue_limit_bytes): 0 = no byte limit, else B + 1 in 64 bits; the mode is q_limit's
+        # bit, so a queue with a byte limit alone holds the largest count there, which bounds nothing
+        ql = qb = 0
+        nbytes = q.max_length_bytes if self.queue_limit_bytes else None
+        if (q.max_length is not None or nbytes is not None) and q.owner == self.rank:
+            length = self.MAX_LENGTH_TOP if q.max_length is None else min(int(q.max_length), self.MAX_LENGTH_TOP)
+            ql = (length + 1) | (0x80000000 if q.overflow == "reject-publish" else 0)
+            if nbytes is not None:
+                qb = min(int(nbytes), self.MAX_LENGTH_BYTES_TOP) + 1
         self._up_at("q_limit", ql, q.slot, np.uint32)
+        if self.queue_limit_bytes:
+            self._up_at("q_blimit", qb, q.slot, np.uint64)
 
     def queue_dlx_changed(self, q):
         # q_dlx (dp_state.h): 0 = none; 1 = declared, no such exchange now; else its slot + 2.  The
@@ -890,6 +911,13 @@ class GpuDataPlane(ControlState):
     def message_count(self, q):
         """Ready messages of queue slot ``q`` (AMQP Queue.DeclareOk message-count)."""
         return self._u64("q_tail", q) - self._u64("q_head", q)
+
+    def queue_bytes(self, q):
+        """Ready bytes of queue slot ``q`` (queue_limit_bytes on): the body bytes of its ready
+        messages, as the device keeps them in q_bytes."""
+        if not self.queue_limit_bytes:
+            raise RuntimeError("queue_bytes() needs queue_limit_bytes=True")
+        return self._u64("q_bytes", q)
 
     def queue_tail(self, q):
         """Queue position the next enqueue into slot ``q`` gets."""

@@ -83,6 +83,7 @@ class GoldenDataPlane(ControlState):
         self.requeue_items = []           # (q, msg, qpos, expire)
         self.qpos_head = defaultdict(int)  # absolute position of ring[0]
         self.counters = defaultdict(int)
+        self._enq_bytes, self._enq_ringfull = {}, set()
 
     # ------------------------------------------------------------------ hooks
     def channel_opened(self, chan):
@@ -157,6 +158,15 @@ class GoldenDataPlane(ControlState):
 
     def message_count(self, q):
         return len(self.ring[q])
+
+    def queue_bytes(self, q):
+        """Ready bytes of queue slot ``q``: the body bytes of its ring entries, summed over the ring
+        itself (no counter: an independent check of the device's q_bytes)."""
+        return sum(len(m.body) for m, _, _ in self.ring[q])
+
+    def _byte_limit(self, qq):
+        """The queue's x-max-length-bytes as enforced here (None: none, or the option off)."""
+        return qq.max_length_bytes if self.queue_limit_bytes else None
 
     def purge(self, q):
         ring = self.ring[q]
@@ -607,6 +617,8 @@ class GoldenDataPlane(ControlState):
         inputs = inputs or {}
         self.counters = defaultdict(int)
         cnt = self.counters
+        self._enq_bytes = {}   # the step's enqueue: queue slot -> Y + the body sizes of its pairs so far
+        self._enq_ringfull = set()   # and the queues whose ring refused one of them
         out = {"egress": {}, "ctrl": [], "txbuf": [], "events": [], "segs": []}
         conns = {c for c in inputs if c in self.conns}   # bytes of a connection closed meanwhile: dropped
         for c, cl in self.carry.items():
@@ -909,11 +921,25 @@ class GoldenDataPlane(ControlState):
         for q in qs:
             qq = self.queue_by_slot[q]
             ring = self.ring[q]
-            if self.queue_limits and qq.max_length is not None and qq.overflow == "reject-publish" \
-                    and len(ring) >= qq.max_length:
+            # x-max-length-bytes, reject-publish (k_byte_room): pair r of the queue's pairs of the step
+            # passes iff Y + E_r < B -- Y the ready bytes when the step's enqueue began, E_r the body
+            # sizes of the queue's earlier pairs of the step, refused ones included (the rule is
+            # monotone, so they only follow a refusal)
+            over_bytes = False
+            blim = self._byte_limit(qq)
+            if blim is not None and qq.overflow == "reject-publish":
+                seen = self._enq_bytes.get(q)
+                if seen is None:
+                    seen = self.queue_bytes(q)
+                over_bytes = seen >= blim
+                self._enq_bytes[q] = seen + len(msg.body)
+            if self.queue_limits and qq.overflow == "reject-publish" and \
+                    ((qq.max_length is not None and len(ring) >= qq.max_length) or over_bytes):
                 # x-max-length, reject-publish (enq_store): refused like a full ring, counted apart;
-                # requeues may have put the depth above the limit (plan_queue grows no ring for these)
-                cnt["n_maxlen_rejected"] += 1
+                # requeues may have put the depth above the limit (plan_queue grows no ring for these).
+                # Where the queue's ring refused an earlier pair of the step, its room was the
+                # smallest of the three and every refusal of the step is the ring's
+                cnt["n_ring_full" if q in self._enq_ringfull else "n_maxlen_rejected"] += 1
                 self._release(msg)
                 if chslot is not None:
                     self.ch[chslot]["pub_fail"] = True
@@ -923,6 +949,7 @@ class GoldenDataPlane(ControlState):
                 if new is not None:
                     self.regrow_ring(qq, new)
             if len(ring) >= qq.capacity:
+                self._enq_ringfull.add(q)
                 cnt["n_ring_full"] += 1
                 self._release(msg)
                 if chslot is not None:   # the publisher gets Basic.Nack for this step's range
@@ -1091,20 +1118,27 @@ class GoldenDataPlane(ControlState):
         return got + out
 
     def _trim(self, q, qq, ring):
-        """x-max-length, drop-head (trim_head in k_dequeue): at the end of the queue's step --
-        after its enqueue, requeues, TTL walk, Basic.Gets and dispatch -- the ready entries above
-        the limit leave from the head like expired ones, 64 an iteration; a durable queue on a
-        persisting plane draws on the TTL walk's record budget and goes on in the next steps."""
-        if not self.queue_limits or qq.max_length is None or qq.overflow != "drop-head":
+        """x-max-length / x-max-length-bytes, drop-head (trim_head in k_dequeue): at the end of the
+        queue's step -- after its enqueue, requeues, TTL walk, Basic.Gets and dispatch -- the ready
+        entries above a limit leave from the head like expired ones, 64 an iteration; a durable
+        queue on a persisting plane draws on the TTL walk's record budget and goes on in the next
+        steps.  Within an iteration, with E_i the exclusive prefix of the body sizes from the head,
+        entry i leaves iff i < depth - L or ready bytes - E_i > B."""
+        blim = self._byte_limit(qq)
+        if not self.queue_limits or (qq.max_length is None and blim is None) or qq.overflow != "drop-head":
             return
         budget_q = self.persist and qq.durable
         dx = self._dx(q)
-        while len(ring) > qq.max_length:
+        over = lambda: (qq.max_length is not None and len(ring) > qq.max_length) or \
+            (blim is not None and self.queue_bytes(q) > blim)
+        while over():
             if budget_q:
                 if self._ttl_budget + 64 > self.persist_max >> 2:
                     break
                 self._ttl_budget += 64
-            for _ in range(min(64, len(ring) - qq.max_length)):
+            for _ in range(64):
+                if not over():
+                    break
                 if dx is not None and not self._dead_leave(q, dx, ring[0], 1, self.step_no):
                     return   # the dead list is full: the next steps go on
                 self._consumed(ring[0][0], q, self.qpos_head[q], 1)

@@ -218,14 +218,14 @@ class GpuPersistence:
         if getattr(p, "queue_limits", False):
             for slot in sorted({it[0] for it in items}):
                 q = p.queue_by_slot.get(slot)
-                if q is not None and q.max_length is not None:
-                    held.append((slot, q.max_length, q.overflow))
+                if q is not None and (q.max_length is not None or getattr(q, "max_length_bytes", None) is not None):
+                    held.append((slot, q.max_length, q.overflow, q.max_length_bytes))
                     p.set_queue_limit(slot, None)
         try:
             return p.restore(items, now_ms)
         finally:
-            for slot, length, mode in held:
-                p.set_queue_limit(slot, length, mode)
+            for slot, length, mode, nbytes in held:
+                p.set_queue_limit(slot, length, mode, nbytes)
 
     # ------------------------------------------------------------------ failover
     def adopt(self, src, queues, now_ms=None):

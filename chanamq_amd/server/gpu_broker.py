@@ -220,7 +220,7 @@ class GpuBroker:
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
                  persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False,
-                 dead_letter=False, x_death=False, alternate_exchange=False):
+                 dead_letter=False, x_death=False, alternate_exchange=False, queue_limit_bytes=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -242,6 +242,14 @@ class GpuBroker:
         self.queue_limits = bool(queue_limits)
         if self.queue_limits and not getattr(plane, "queue_limits", False):
             raise ValueError("queue_limits=True needs a data plane built with queue_limits=True")
+        # byte limits (chana.mq.gpu.queue-limit-bytes): Queue.Declare's x-max-length-bytes is parsed
+        # and passed to the plane (built with queue_limit_bytes=True), under the queue's x-overflow
+        # mode; off, it is ignored as always before
+        self.queue_limit_bytes = bool(queue_limit_bytes)
+        if self.queue_limit_bytes and not self.queue_limits:
+            raise ValueError("queue_limit_bytes=True needs queue_limits=True")
+        if self.queue_limit_bytes and not getattr(plane, "queue_limit_bytes", False):
+            raise ValueError("queue_limit_bytes=True needs a data plane built with queue_limit_bytes=True")
         # dead-lettering (chana.mq.gpu.dead-letter): Queue.Declare's x-dead-letter-exchange /
         # x-dead-letter-routing-key are parsed and passed to the plane (built with dead_letter=True,
         # which serves them); off, they are ignored as always before.  Single node only
@@ -512,6 +520,9 @@ class GpuBroker:
             out = [{"vhost": q.vhost, "name": q.name, "durable": q.durable, "owner": q.owner,
                     "ready": self.plane.message_count(q.slot) if q.owner == self.plane.rank else None,
                     "consumers": len(q.consumers)} for q in self.plane.queues.values()]
+            if self.queue_limit_bytes:   # the body bytes of the ready messages, beside their count
+                for row, q in zip(out, self.plane.queues.values()):
+                    row["ready_bytes"] = self.plane.queue_bytes(q.slot) if q.owner == self.plane.rank else None
         return json.dumps(out)
 
     # ------------------------------------------------------------------ pipelined native loop
@@ -1563,7 +1574,7 @@ class GpuBroker:
     def _limit_args(self, m, q=None):
         """Queue.Declare's x-max-length / x-overflow as ``declare_queue`` keywords, with
         queue-limits on ({} with it off, or without a limit: the arguments are ignored as always
-        before; x-max-length-bytes stays ignored).  A length that is no integer >= 0, or a mode
+        before; x-max-length-bytes too unless queue-limit-bytes is on).  A value that is no integer >= 0, or a mode
         other than drop-head / reject-publish, is 406 PRECONDITION_FAILED with nothing changed.
         ``q`` (the sharded submit only, which must refuse before anything is replicated): the
         existing queue, whose limit the declare must not differ from; on a single node
@@ -1574,16 +1585,30 @@ class GpuBroker:
         ov = args.get("x-overflow")
         if ov is not None and ov not in self.plane.OVERFLOW_MODES:
             raise ControlError(C.PRECONDITION_FAILED, f"invalid x-overflow {ov!r}", 50, 10)
-        if "x-max-length" not in args:
-            return {}
-        v = args["x-max-length"]
-        if isinstance(v, Typed) and v.tag in "bBsuIil":
-            v = v.value
-        length, ov = self.plane.check_limit(v, ov)
-        if q is not None and not m.passive and q.max_length is not None and (q.max_length, q.overflow) != (length, ov):
-            raise ControlError(C.PRECONDITION_FAILED, f"queue '{q.name}' is declared with x-max-length "
-                               f"{q.max_length} ({q.overflow})", 50, 10)
-        return dict(max_length=length, overflow=ov)
+        def integer(name):
+            v = args[name]
+            return v.value if isinstance(v, Typed) and v.tag in "bBsuIil" else v
+        out = {}
+        # x-max-length-bytes (queue-limit-bytes on; off: ignored as always before): by the rules of
+        # x-max-length -- any AMQP integer type, kept in 64 bits, 406 when it is no integer >= 0
+        if self.queue_limit_bytes and "x-max-length-bytes" in args:
+            nbytes, ov = self.plane.check_limit_bytes(integer("x-max-length-bytes"), ov)
+            out.update(max_length_bytes=nbytes, overflow=ov)
+        if "x-max-length" in args:
+            length, ov = self.plane.check_limit(integer("x-max-length"), ov)
+            out.update(max_length=length, overflow=ov)
+        if q is not None and not m.passive and out:
+            length, nbytes = out.get("max_length"), out.get("max_length_bytes")
+            if length is not None and q.max_length is not None and (q.max_length, q.overflow) != (length, ov):
+                raise ControlError(C.PRECONDITION_FAILED, f"queue '{q.name}' is declared with x-max-length "
+                                   f"{q.max_length} ({q.overflow})", 50, 10)
+            if nbytes is not None and q.max_length_bytes is not None and (q.max_length_bytes, q.overflow) != (nbytes, ov):
+                raise ControlError(C.PRECONDITION_FAILED, f"queue '{q.name}' is declared with x-max-length-bytes "
+                                   f"{q.max_length_bytes} ({q.overflow})", 50, 10)
+            if (q.max_length is not None or q.max_length_bytes is not None) and q.overflow != ov:
+                raise ControlError(C.PRECONDITION_FAILED, f"queue '{q.name}' is declared with x-overflow "
+                                   f"{q.overflow}", 50, 10)
+        return out
 
     def _bind_args(self, m):
         """The arguments of a Queue.Bind / Unbind / Exchange.Bind / Unbind as the plane takes

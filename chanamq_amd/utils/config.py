@@ -292,6 +292,12 @@ class Config:
         queue_limits = bool(g(k + "queue-limits", False))
         if queue_limits:
             plane.update(queue_limits=True)
+        # queues honour Queue.Declare's x-max-length-bytes under their x-overflow mode (needs queue-limits)
+        queue_limit_bytes = bool(g(k + "queue-limit-bytes", False))
+        if queue_limit_bytes:
+            if not queue_limits:
+                raise ValueError("chana.mq.gpu.queue-limit-bytes needs chana.mq.gpu.queue-limits")
+            plane.update(queue_limit_bytes=True)
         # queues honour Queue.Declare's x-dead-letter-exchange / x-dead-letter-routing-key (off: ignored)
         dead_letter = bool(g(k + "dead-letter", False))
         if dead_letter:
@@ -318,7 +324,7 @@ class Config:
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
                       headers_match=headers_match, queue_limits=queue_limits, dead_letter=dead_letter, x_death=x_death,
-                      alternate_exchange=alternate_exchange,
+                      alternate_exchange=alternate_exchange, queue_limit_bytes=queue_limit_bytes,
                       mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 

@@ -2127,7 +2127,9 @@ struct EnqLoad {
   i64 expire_ms = 0, ttl = 0;
   bool durable = false;
   u32 ql = 0;   // the queue's length limit (q_limit; 0 with DS.limits off)
+  u32 kq = INVALID;   // BL: K_q of a reject-publish queue with a byte limit (q_broom; INVALID: no such limit)
 };
+template <bool BL = false>   // DS.blimits as a compile-time constant, like DLX: the flag-off kernels hold none of it
 DEV EnqLoad enq_load(const DS& d, u32 q, u32 p) {
   const Pub& pb = d.pubs[p];
   EnqLoad e;
@@ -2144,6 +2146,9 @@ DEV EnqLoad enq_load(const DS& d, u32 q, u32 p) {
   e.ttl = d.q_ttl[q];
   e.durable = d.persist && d.q_durable[q];
   if (d.limits) e.ql = d.q_limit[q];   // kernel-uniform
+  if (BL) {
+    if (ql_reject(e.ql) && d.q_blimit[q]) e.kq = d.q_broom[q];
+  }
   return e;
 }
 // `limited`: the dropped pair was refused by the queue's x-max-length (reject-publish), not by its ring
@@ -2161,6 +2166,9 @@ DEV u32 enq_store(const DS& d, const EnqLoad& l, u32 q, u32 rank, bool last, Per
     const u64 room = len > depth ? len - depth : 0;
     if (room <= freec) { freec = room; *limited = true; }
   }
+  // x-max-length-bytes, reject-publish: the first K_q pairs of the queue pass the byte rule
+  // (k_byte_room); asked before the ring like the count limit, and the smaller of the two decides
+  if (l.kq != INVALID && l.kq <= freec) { freec = l.kq; *limited = true; }
   if (rank < freec) {
     u64 pos = l.tail + rank;
     Desc ds;
@@ -2184,13 +2192,14 @@ DEV u32 enq_store(const DS& d, const EnqLoad& l, u32 q, u32 rank, bool last, Per
   }
   return drop;
 }
+template <bool BL>
 DEV u32 enqueue_one(const DS& d, u32 src, u32 i, u32 n, PersistRec* pr, bool* limited) {
   const u32* kk = d.pair_k[src];
   const u32 rb = d.rank_bits;
   u32 q = kk[i] >> rb;
   u32 p = d.pair_v[src][i];
   u32 first = d.q_first[q];   // the queue's first pair (k_qfirst)
-  return enq_store(d, enq_load(d, q, p), q, i - first, (i + 1 == n) || (kk[i + 1] >> rb) != q, pr, limited);
+  return enq_store(d, enq_load<BL>(d, q, p), q, i - first, (i + 1 == n) || (kk[i + 1] >> rb) != q, pr, limited);
 }
 // after a pair's enqueue (whole waves: wave collectives): release the message a full ring
 // (or a reject-publish queue at its limit) dropped and count it by the reason; record a
@@ -2211,6 +2220,7 @@ DEV void enqueue_done(const DS& d, u32 drop, bool limited, const PersistRec& pr)
 // ring pool (one bump pointer shared with the host's allocator), within the queue's
 // max_capacity.  Positions stay absolute (entry pos lives at off + (pos & mask)), so
 // unacked windows, requeues and store rows keep their queue offsets.
+template <bool BL = false>
 DEV void plan_queue(const DS& d, u32 q, u64 cnt);
 // copy every moved (grown) ring's live entries to its new place, by the nt threads of a block
 DEV void copy_moved_rings(const DS& d, u32 nm, u32 tid, u32 nt) {
@@ -2221,14 +2231,16 @@ DEV void copy_moved_rings(const DS& d, u32 nm, u32 tid, u32 nt) {
   }
 }
 
+template <bool BL>
 DEV void ring_plan_one(const DS& d, u32 src, u32 i, u32 n) {
   const u32* kk = d.pair_k[src];
   const u32 rb = d.rank_bits;
   const u32 q = kk[i] >> rb;
   if (i + 1 < n && (kk[i + 1] >> rb) == q) return;   // not the queue's last pair
-  plan_queue(d, q, (u64)(i - d.q_first[q]) + 1);
+  plan_queue<BL>(d, q, (u64)(i - d.q_first[q]) + 1);
 }
 // queue q takes cnt entries this step: record its tail before the enqueue, grow its ring
+template <bool BL>
 DEV void plan_queue(const DS& d, u32 q, u64 cnt) {
   const u64 head = d.q_head[q], tail = d.q_tail[q];
   d.q_enq_tail[q] = tail;
@@ -2238,6 +2250,9 @@ DEV void plan_queue(const DS& d, u32 q, u64 cnt) {
       const u64 depth = tail - head, len = ql_len(ql);
       const u64 room = len > depth ? len - depth : 0;
       if (cnt > room) cnt = room;
+      if (BL) {   // and no more than pass its byte rule (K_q): no ring grows for pairs it will refuse
+        if (d.q_blimit[q] && cnt > d.q_broom[q]) cnt = d.q_broom[q];
+      }
     }
   }
   const u64 mask = d.q_ring_mask[q], cap = mask + 1;
@@ -2273,13 +2288,14 @@ DEV void plan_queue(const DS& d, u32 q, u64 cnt) {
 // k_ring_moves: growth is rare, so one block does it and the common step saves a launch)
 // Grid-stride over the pairs with a capped grid (the graph's grid is sized for pair_max;
 // a block per 256 pairs of the capacity would mostly launch waves with nothing to do)
+template <bool BL>
 __global__ __launch_bounds__(256) void k_ring_plan(DS d, u32 src) {
   __shared__ u32 s_last;
   const u32 n = d.tot[TS_PAIR_N];
   u32 nb = (n + 255) / 256;
   if (nb > gridDim.x) nb = gridDim.x;   // blocks taking part
   if (blockIdx.x >= nb) return;
-  for (u32 i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) ring_plan_one(d, src, i, n);
+  for (u32 i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) ring_plan_one<BL>(d, src, i, n);
   // a thread that planned a ring move fenced it itself (rare); the common step only waits
   // for its own stores before the ticket (no L2 writeback per block)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -2292,6 +2308,60 @@ __global__ __launch_bounds__(256) void k_ring_plan(DS d, u32 src) {
   copy_moved_rings(d, d.tot[TS_NMOVE], threadIdx.x, 256);
 }
 
+// x-max-length-bytes, reject-publish (DS.blimits): K_q of the step for every queue that has pairs
+// and such a limit -- how many of its pairs, in sort order, pass "ready bytes + the body sizes of
+// the queue's earlier pairs of the step < B".  The rule is monotone, so the count is a prefix.
+// Waves stride over the sorted pairs; a lane that holds the first pair of such a queue names it,
+// and the whole wave then walks that queue's pairs 64 at a time with a prefix scan of their
+// body sizes, up to the first pair that fails.  Runs behind the sort, ahead of k_ring_plan and
+// k_enqueue, which read K_q (q_broom); q_bytes is what the last step's k_dequeue (and a
+// Basic.Get between steps) left.
+__global__ __launch_bounds__(256) void k_byte_room(DS d, u32 src) {
+  const u32 n = d.tot[TS_PAIR_N];
+  const u32* kk = d.pair_k[src];
+  const u32* vv = d.pair_v[src];
+  const u32 rb = d.rank_bits, lane = lane_id();
+  const u32 wv = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+  for (u32 b = wv * 64; b < n; b += nw * 64) {   // (wave-uniform)
+    const u32 i = b + lane;
+    u32 q = INVALID;
+    bool first = false;
+    if (i < n) {
+      q = kk[i] >> rb;
+      first = i == 0 || (kk[i - 1] >> rb) != q;
+    }
+    bool mine = false;
+    if (first && q < d.q_max) mine = ql_reject(d.q_limit[q]) && d.q_blimit[q] != 0;
+    u64 todo = __ballot(mine);
+    while (todo) {
+      const u32 l0 = (u32)__ffsll((unsigned long long)todo) - 1u;
+      todo &= todo - 1;
+      const u32 qq = (u32)__shfl((int)q, l0, 64);
+      const u32 i0 = b + l0;
+      const u64 B = d.q_blimit[qq] - 1;
+      u64 y = d.q_bytes[qq];   // Y + the sizes of the pairs walked so far
+      u32 k = 0;
+      for (u32 j0 = i0; j0 < n; j0 += 64) {
+        const u32 j = j0 + lane;
+        const bool in = j < n && (kk[j] >> rb) == qq;
+        const u64 sz = in ? d.pubs[vv[j]].body_size : 0u;
+        const u64 incl = wave_incl_scan64(sz);
+        const u64 inm = __ballot(in);
+        // the queue's pairs are contiguous: `in` is a prefix of the lanes, and so is `pass` within it
+        const u32 nin = (u32)__popcll(inm);
+        const u32 np = (u32)__popcll(__ballot(in && y + (incl - sz) < B));
+        k += np;
+        if (np < 64u || nin < 64u) break;
+        y += shfl64(incl, 63);
+      }
+      if (lane == 0) d.q_broom[qq] = k;
+    }
+  }
+}
+
+// BL: the bytes of the accepted pairs join q_bytes, one atomic per (wave, queue) run -- the pairs
+// are sorted by queue, so a queue's lanes are contiguous
+template <bool BL>
 __global__ void k_enqueue(DS d, u32 src) {
   const u32 n = d.tot[TS_PAIR_N];
   const u32 stride = gridDim.x * blockDim.x;
@@ -2301,7 +2371,26 @@ __global__ void k_enqueue(DS d, u32 src) {
     PersistRec pr;
     pr.msg = INVALID;
     bool limited = false;
-    u32 drop = i < n ? enqueue_one(d, src, i, n, &pr, &limited) : INVALID;
+    u32 drop = i < n ? enqueue_one<BL>(d, src, i, n, &pr, &limited) : INVALID;
+    if (BL) {
+      const u32 lane = lane_id();
+      u32 q = INVALID;
+      u64 sz = 0;
+      if (i < n) {
+        q = d.pair_k[src][i] >> d.rank_bits;
+        const u32 msg = d.pubs[d.pair_v[src][i]].msg;
+        if (drop == INVALID && msg != INVALID) sz = d.msgs[msg].body_len;   // stored (exact under any cut)
+      }
+      const u64 incl = wave_incl_scan64(sz);
+      const u32 qprev = (u32)__shfl_up((int)q, 1, 64), qnext = (u32)__shfl_down((int)q, 1, 64);
+      const bool head = lane == 0 || qprev != q, last = lane == 63 || qnext != q;
+      const u64 heads = __ballot(head);
+      // the run's first lane: the highest head at or below this lane
+      const u32 l0 = 63u - (u32)__clzll((unsigned long long)(heads & (lanemask_lt() | (1ull << lane))));
+      const u64 before = shfl64(incl - sz, l0);
+      if (last && q != INVALID && incl != before)
+        atomicAdd((unsigned long long*)&d.q_bytes[q], (unsigned long long)(incl - before));
+    }
     enqueue_done(d, drop, limited, pr);
   }
 }
@@ -2786,6 +2875,7 @@ DEV void unreserve(const DS& d, u32 c, u32 take) {
 // over individual deliveries is needed (QueueEntity.scala:318-393, FrameStage.scala:380-406).
 #define REQ_BLK 1024
 DEV void requeue_compact(const DS& d);
+template <bool BL>
 DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p);
 // one queue's share of a spill (4 waves): every queued message past the first `hot` entries
 // (of a queue with consumers) whose slot lies below log position `lim` -- its body to the
@@ -2859,31 +2949,60 @@ struct DqCons { u32 c, ch, ok, noack, pc, glob, unacked; };
 // with a head that passes them (spill_queue restarts at the head; k_dequeue, k_cold_scan and
 // k_cold_commit compare them with the head).  Stores q_head[q] if it moved; a dead-letter
 // exchange would take the trimmed entries here.
-template <bool DLX>
-DEV void trim_head(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc* ring) {
+// BL (x-max-length-bytes): `bytes` are the queue's ready bytes at `head`; the trim also runs while
+// they exceed the byte limit B.  An iteration looks at the (up to) 64 entries at the head, their
+// body sizes loaded together: with E_i the exclusive prefix of the sizes, entry i leaves iff
+// i < depth - L or bytes - E_i > B -- both monotone in i, so the drop count is one ballot.  One
+// body larger than B leaves an empty queue.  Stores q_bytes[q], for every queue, limited or not
+// (this is where the queue's step ends).
+template <bool DLX, bool BL>
+DEV void trim_head(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc* ring, u64 bytes) {
   const u32 ql = d.q_limit[q];
-  if (!ql_set(ql) || ql_reject(ql)) return;   // wave-uniform
-  const u64 len = ql_len(ql);
-  if (tail - head <= len) return;
   const u32 lane = lane_id();
+  if (!ql_set(ql) || ql_reject(ql)) {   // wave-uniform
+    if (BL && lane == 0) d.q_bytes[q] = bytes;
+    return;
+  }
+  const u64 len = ql_len(ql);
+  u64 bl = 0;   // BL: 0, or B + 1
+  if (BL) bl = d.q_blimit[q];
+  if (tail - head <= len && !(BL && bl && bytes >= bl)) {
+    if (BL && lane == 0) d.q_bytes[q] = bytes;
+    return;
+  }
   const bool budget = d.persist && d.q_durable[q];
   // DS.dlx, a queue with a dead-letter exchange: as in the TTL walk, the trimmed entries join
   // the dead list as far as it has room, and the trim ends where bodies may be cold
   const u32 dx = DLX ? d.dl->q_dlx[q] : 0u;   // wave-uniform
   const u64 clim = dx ? d.q_cold_lim[q] : ~0ull;
-  while (tail - head > len && head < clim) {
+  while ((tail - head > len || (BL && bl && bytes >= bl)) && head < clim) {
     if (budget) {
       u32 ok = 1;
       if (lane == 0) ok = atomicAdd(&d.tot[TS_TTL_BUDGET], 64u) + 64u <= (d.persist_max >> 2);
       if (!__shfl(ok, 0, 64)) break;
     }
-    u64 over = tail - head - len;
-    if (over > clim - head) over = clim - head;
-    u32 n = over < 64 ? (u32)over : 64u;
     const u64 idx = head + lane;
     Desc ds;
     ds.msg = INVALID; ds.expire_ms = 0; ds.flags = 0;
-    if (lane < n) ds = ring[idx & mask];
+    u32 n;
+    u32 esz = 0;   // BL: the entry's body bytes
+    if (!BL) {
+      u64 over = tail - head - len;
+      if (over > clim - head) over = clim - head;
+      n = over < 64 ? (u32)over : 64u;
+      if (lane < n) ds = ring[idx & mask];
+    } else {
+      const u64 over = tail - head > len ? tail - head - len : 0;
+      u64 span = tail - head;
+      if (span > clim - head) span = clim - head;
+      const u32 w = span < 64 ? (u32)span : 64u;   // the entries looked at
+      if (w == 0) break;   // (an empty queue holds no bytes)
+      if (lane < w) ds = ring[idx & mask];
+      if (lane < w && ds.msg != INVALID) esz = d.msgs[ds.msg].body_len;
+      const u64 excl = wave_incl_scan64(esz) - esz;
+      n = (u32)__popcll(__ballot(lane < w && (lane < over || (bl && bytes - excl >= bl))));
+      if (lane >= n) { ds.msg = INVALID; ds.expire_ms = 0; ds.flags = 0; }
+    }
     bool full = false;
     if (dx) {
       const u32 left = dead_leave(d, dx, (u32)d.in->step, ds.msg, ds.expire_ms, q, idx, DL_MAXLEN, n);
@@ -2894,12 +3013,14 @@ DEV void trim_head(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc*
     wave_consumed(d, ds.msg, q, idx, 1u, v);
     if (!dx) wave_release(d, ds.msg, v);
     if (lane == 0 && n) atomicAdd(&d.ctr->n_maxlen_dropped, n);
+    if (BL) bytes -= (u64)wave_sum64(v ? (i64)esz : 0);
     head += n;
     if (full) break;
   }
   if (lane == 0) d.q_head[q] = head;
+  if (BL && lane == 0) d.q_bytes[q] = bytes;
 }
-template <bool DLX>
+template <bool DLX, bool BL>
 DEV bool dequeue_queue(const DS& d) {
   __shared__ u32 g_cons[RUNS_PER_Q];
   __shared__ u32 g_n[RUNS_PER_Q];
@@ -2907,6 +3028,7 @@ DEV bool dequeue_queue(const DS& d) {
   __shared__ u64 s_head;
   __shared__ u32 s_ngr;
   __shared__ unsigned long long s_bytes;
+  __shared__ u64 s_qb;   // BL: the queue's ready bytes as the step's walks leave them (wave 0 / thread 0)
   __shared__ u64 kpos[REQ_BLK];
   __shared__ u32 kidx[REQ_BLK];
   __shared__ u32 rq_cnt, rq_last;
@@ -2923,7 +3045,7 @@ DEV bool dequeue_queue(const DS& d) {
   // changes in the compaction, which runs after every block has read it); the last one
   // compacts the unconsumed items
   if (*d.req_n != 0) {
-    if (q < d.q_max && d.req_q_n[q] != 0) requeue_queue(d, q, kpos, kidx, &rq_cnt);
+    if (q < d.q_max && d.req_q_n[q] != 0) requeue_queue<BL>(d, q, kpos, kidx, &rq_cnt);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     if (tid == 0) rq_last = atomicAdd(&d.tot[TS_REQ_TICKET], 1u) == gridDim.x - 1;
@@ -2983,6 +3105,9 @@ DEV bool dequeue_queue(const DS& d) {
     const u32 dx = DLX ? d.dl->q_dlx[q] : 0u;   // wave-uniform
     u64 wend = tail;
     if (dx && d.q_cold_lim[q] < wend) wend = d.q_cold_lim[q];
+    // BL: the ready bytes before the walk (agent scope, like the head: the requeue above added to them)
+    u64 qb = 0;
+    if (BL) qb = __hip_atomic_load(&d.q_bytes[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     while (head < wend) {
       if (budget) {
         u32 ok = 1;
@@ -2997,6 +3122,10 @@ DEV bool dequeue_queue(const DS& d) {
       bool exp = valid && ds.expire_ms != 0 && ds.expire_ms <= now;
       u64 live = __ballot(valid && !exp);
       u32 nexp = live ? (__ffsll((unsigned long long)live) - 1) : __popcll(__ballot(valid));
+      u32 esz = 0;   // BL: the leaving entry's body bytes (read before its release)
+      if (BL) {
+        if (lane < nexp && ds.msg != INVALID) esz = d.msgs[ds.msg].body_len;
+      }
       bool full = false;
       if (dx) {
         const u32 left = dead_leave(d, dx, (u32)d.in->step, ds.msg, ds.expire_ms, q, idx, DL_EXPIRED, nexp);
@@ -3006,10 +3135,12 @@ DEV bool dequeue_queue(const DS& d) {
       wave_consumed(d, ds.msg, q, idx, 1u, lane < nexp);
       if (!dx) wave_release(d, ds.msg, lane < nexp);
       if (lane == 0 && nexp) atomicAdd(&d.ctr->n_expired, nexp);
+      if (BL) qb -= (u64)wave_sum64(lane < nexp ? (i64)esz : 0);
       head += nexp;
       if (live || full) break;
     }
     if (lane == 0) { s_head = head; s_bytes = 0; }
+    if (BL && lane == 0) s_qb = qb;
   } else if (!nodisp && tid - 64 < RUNS_PER_Q) {   // the consumers' inputs, beside the TTL walk
     const u32 j = tid - 64, mall0 = d.q_cons_n[q];
     if (j < mall0) {
@@ -3043,6 +3174,7 @@ DEV bool dequeue_queue(const DS& d) {
       const u32 ng = d.in->nget < GET_STEP_MAX ? d.in->nget : GET_STEP_MAX;
       const u64 clim = d.q_cold_lim[q];   // a cold head waits for the host's page-in (RETRY)
       u64 h = head;
+      u64 gbytes = 0;   // BL: body bytes of the entries the answers take
       // the host-staged requests (their connections were paused: nothing of theirs was
       // decoded this step), then the step's own Basic.Gets in wire order
       for (u32 i = 0; i < ng + ndg; ++i) {
@@ -3083,6 +3215,7 @@ DEV bool dequeue_queue(const DS& d) {
             rn.noack = rq.noack ? 1u : 0u;
             rn.flags = RUN_GET;
             d.runs[(u64)q * RUNS_PER_Q + ngr] = rn;
+            if (BL) gbytes += d.msgs[ring[h & mask].msg].body_len;
             ++ngr;
             ++h;
             o.status = GS_OK;
@@ -3100,6 +3233,7 @@ DEV bool dequeue_queue(const DS& d) {
       }
       s_head = h;
       s_ngr = ngr;
+      if (BL) s_qb -= gbytes;
     }
     __syncthreads();
     head = s_head;
@@ -3112,7 +3246,7 @@ DEV bool dequeue_queue(const DS& d) {
   if (mall == 0 || avail == 0 || nodisp) {
     if (tid == 0) { d.q_head[q] = head; d.q_nruns[q] = ngr; }
     // (wave 0: thread 0's store of q_head above is ordered before lane 0's in trim_head)
-    if (d.limits && tid < 64) trim_head<DLX>(d, q, head, tail, mask, ring);
+    if (d.limits && tid < 64) trim_head<DLX, BL>(d, q, head, tail, mask, ring, BL ? s_qb : 0ull);
     return true;
   }
   const u32 m = mall > RUNS_PER_Q - ngr ? RUNS_PER_Q - ngr : mall;
@@ -3251,10 +3385,33 @@ DEV bool dequeue_queue(const DS& d) {
     d.q_head[q] = qp;
     d.q_rr[q] = (r + 1) % mall;
     if (d.limits) s_head = qp;
+    if (BL) s_bytes = 0;   // (read above; the block sums the dispatched entries' body bytes into it next)
   }
   if (d.limits) {   // kernel-uniform: the step's final head through LDS to wave 0
     __syncthreads();
-    if (tid < 64) trim_head<DLX>(d, q, s_head, tail, mask, ring);
+    if (BL) {
+      // the body bytes of what the dispatch took, [head, s_head): summed once the budget and slot
+      // cuts of (3) have fixed the runs, so the count is exact under any cut; four entries a
+      // thread per round, their ring loads then their message loads in flight together
+      const u64 hend = s_head;
+      constexpr u32 U = 4;
+      u64 took = 0;
+      for (u64 k0 = head + tid; k0 < hend; k0 += 256 * U) {
+        u32 mg[U];
+#pragma unroll
+        for (u32 u = 0; u < U; ++u) {
+          const u64 k = k0 + (u64)u * 256;
+          mg[u] = k < hend ? ring[k & mask].msg : INVALID;
+        }
+#pragma unroll
+        for (u32 u = 0; u < U; ++u)
+          if (mg[u] != INVALID) took += d.msgs[mg[u]].body_len;
+      }
+      took = (u64)wave_sum64((i64)took);
+      if (lane == 0 && took) atomicAdd(&s_bytes, (unsigned long long)took);
+      __syncthreads();
+    }
+    if (tid < 64) trim_head<DLX, BL>(d, q, s_head, tail, mask, ring, BL ? s_qb - s_bytes : 0ull);
   }
   return true;
 }
@@ -3263,12 +3420,12 @@ DEV bool dequeue_queue(const DS& d) {
 // step's delivery runs (runs_body, once the kernel k_runs: a launch less per step)
 template <u32 NT> DEV void runs_body(const DS& d, u64* key_lds, u32 key_cap, u32* lds);
 #define DQ_RUN_LDS 2048   // runs that runs_body sorts in LDS (more: the global-memory sort)
-template <bool DLX>
+template <bool DLX, bool BL = false>
 __global__ __launch_bounds__(256) void k_dequeue(DS d) {
   __shared__ u64 key_lds[DQ_RUN_LDS];
   __shared__ u32 lds[256 / 64 + 1];
   __shared__ u32 s_last;
-  const bool wrote = dequeue_queue<DLX>(d);
+  const bool wrote = dequeue_queue<DLX, BL>(d);
   // every block's runs and counts reach the device-wide coherence point before its ticket
   // (agent scope: the last block may run on another XCD, whose L2 does not see this one's);
   // a block that wrote no runs stored its zero count agent-coherent and skips the L2
@@ -4096,6 +4253,8 @@ DEV void host_out_copies(const DS& d, u64 gtid, u64 gsz) {
 // DS.dlx, a queue with a dead-letter exchange: the expired entries join the dead list, stamped
 // with `step` (the last step submitted), and the next step's dead pass takes them; where the
 // list has no room the answer is GetEmpty (the entries behind wait for a step to drain it)
+// BL (DS.blimits): the skipped entries and the one handed out leave q_bytes
+template <bool BL>
 __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack, i64 now, u8* out, u64 out_cap,
                                                   GetRes* res, u32 step) {
   u32 lane = lane_id();
@@ -4104,6 +4263,8 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
   const Desc* ring = d.ring + d.q_ring_off[q];
   u32 nexp = 0;
   bool more_expired = false, full = false;
+  u64 qb = 0;   // BL: the queue's ready bytes
+  if (BL) qb = d.q_bytes[q];
   const u32 dx = d.dlx ? d.dl->q_dlx[q] : 0u;
   if (head < tail) {
     u64 idx = head + lane;
@@ -4115,6 +4276,10 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
     u64 live = __ballot(valid && !exp);
     nexp = live ? (__ffsll((unsigned long long)live) - 1) : __popcll(__ballot(valid));
     more_expired = !live && head + nexp < tail;
+    u32 esz = 0;
+    if (BL) {
+      if (lane < nexp && ds.msg != INVALID) esz = d.msgs[ds.msg].body_len;   // (before the release)
+    }
     if (dx) {
       const u32 left = dead_leave(d, dx, step, ds.msg, ds.expire_ms, q, idx, DL_EXPIRED, nexp);
       full = left < nexp;
@@ -4134,6 +4299,7 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
     }
     if (!dx) wave_release(d, ds.msg, mine);
     if (lane == 0) res->n_exp = __popcll(rm);
+    if (BL) qb -= (u64)wave_sum64(mine ? (i64)esz : 0);
     head += nexp;
   } else if (lane == 0) {
     res->n_exp = 0;
@@ -4141,6 +4307,7 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
   if (head >= tail || more_expired || full) {
     if (lane == 0) {
       d.q_head[q] = head;
+      if (BL) d.q_bytes[q] = qb;
       res->status = (more_expired && !full) ? GET_RETRY : GET_EMPTY;
       res->msg_count = (u32)(tail - head);
       res->out_len = 0;
@@ -4150,6 +4317,7 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
   if (head >= d.q_cold_lim[q] && (d.msgs[ring[head & mask].msg].log_off & COLD_BIT)) {
     if (lane == 0) {   // the host pages the queue's head back in, then asks again
       d.q_head[q] = head;
+      if (BL) d.q_bytes[q] = qb;
       res->status = GET_COLD;
       res->msg_count = (u32)(tail - head);
       res->out_len = 0;
@@ -4170,6 +4338,7 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
   if (st != GET_OK) {
     if (lane == 0) {
       d.q_head[q] = head;
+      if (BL) d.q_bytes[q] = qb;
       res->status = st;
       res->msg_count = (u32)(tail - head);
       res->out_len = 0;
@@ -4197,6 +4366,7 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
       *d.n_dirty = k + 1;
     }
     d.q_head[q] = head + 1;
+    if (BL) d.q_bytes[q] = qb - m.body_len;
     res->status = GET_OK;
     res->msg_count = msg_count;
     res->out_len = (u32)need;
@@ -4513,6 +4683,9 @@ DEV u32 requeue_gather(const DS& d, u32 q, u32 n, u64 lo, u64 hi, bool keep, u64
 
 // the m gathered items sorted by queue position; the first k of them written to ring
 // positions base, base + 1, .. and taken off the list
+// BL: the pushed entries' bytes go back into q_bytes (atomics: the block's waves; the queue's block
+// reads the sum agent-scope once its requeue is done)
+template <bool BL>
 DEV void requeue_sort_push(const DS& d, u32 q, u64* kpos, u32* kidx, u32 m, u32 k, u64 base, u64 mask) {
   const u32 tid = threadIdx.x;
   u32 np2 = 1;
@@ -4534,6 +4707,7 @@ DEV void requeue_sort_push(const DS& d, u32 q, u64* kpos, u32* kidx, u32 m, u32 
       __syncthreads();
     }
   }
+  u64 back = 0;
   for (u32 i = tid; i < k; i += 256) {
     const ReqItem r = d.req[kidx[i]];
     Desc ds;
@@ -4543,10 +4717,16 @@ DEV void requeue_sort_push(const DS& d, u32 q, u64* kpos, u32* kidx, u32 m, u32 
     d.ring[d.q_ring_off[q] + ((base + i) & mask)] = ds;
     // consumed (agent-coherent: the compacting block of another XCD reads it after the ticket)
     __hip_atomic_store(&d.req[kidx[i]].q, INVALID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (BL) back += d.msgs[r.msg].body_len;
+  }
+  if (BL) {
+    back = (u64)wave_sum64((i64)back);
+    if (lane_id() == 0 && back) atomicAdd((unsigned long long*)&d.q_bytes[q], (unsigned long long)back);
   }
   __syncthreads();
 }
 
+template <bool BL>
 DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p) {
   const u32 tid = threadIdx.x;
   u32 n = *d.req_n;
@@ -4558,7 +4738,7 @@ DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p) {
   u32 done = 0;
   if (total <= REQ_BLK) {
     done = total < freec ? total : (u32)freec;   // (no room for all: the lowest positions)
-    requeue_sort_push(d, q, kpos, kidx, total, done, head - done, mask);
+    requeue_sort_push<BL>(d, q, kpos, kidx, total, done, head - done, mask);
   } else {
     // the positions' bounds (kpos[0..1] as scratch: the gathers below rewrite them)
     if (tid == 0) { kpos[0] = ~0ull; kpos[1] = 0; }
@@ -4596,7 +4776,7 @@ DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p) {
       }
       if (lo == hi) break;   // more than REQ_BLK items at one position: they stay listed
       const u32 m = requeue_gather(d, q, n, lo, hi, true, kpos, kidx, cnt_p);
-      requeue_sort_push(d, q, kpos, kidx, m, m, head - done - m, mask);
+      requeue_sort_push<BL>(d, q, kpos, kidx, m, m, head - done - m, mask);
       done += m;
       hi = lo;
     }

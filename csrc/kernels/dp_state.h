@@ -382,6 +382,18 @@ struct DS {
   // ---------------- alternate exchanges (alternate-exchange): read only by the ALT instantiations of
   // routing pass 0, which the engine launches with the option on
   i32* x_alt;               // [x_max] slot of the exchange's alternate exchange as it exists now, or -1
+
+  // ---------------- queue byte limits (x-max-length-bytes; blimits == 0: nothing below is read).  Read and
+  // written only by the BL instantiations of the enqueue / dequeue kernels and by k_byte_room, which the
+  // engine launches with the option on (it needs limits: the overflow mode is q_limit's QL_REJECT bit, and
+  // a queue with a byte limit alone holds q_limit = (QL_MAX + 1) | mode, a count that bounds nothing)
+  u32 blimits;              // kernel-uniform, like limits
+  u64* q_blimit;            // [q_max] 0: no byte limit; else B + 1 (64 bits: B = 2^32 + 5 is not 5)
+  u64* q_bytes;             // [q_max] ready bytes: the sum of MsgEnt.body_len over the ring entries in
+                            // [q_head, q_tail), kept for every queue (a later declare may bring a limit)
+  u32* q_broom;             // [q_max] K_q of the step (k_byte_room): how many of the queue's pairs, in sort
+                            // order, pass the reject-publish byte rule; written for the queues that have
+                            // pairs and such a limit, read for no other
 };
 struct DlState {
   u32 dead_max;             // items of the dead list (<= DEAD_LIST_MAX)

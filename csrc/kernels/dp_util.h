@@ -142,6 +142,16 @@ DEV i64 wave_sum64(i64 v) {
   }
   return (i64)x;
 }
+// inclusive prefix sum over the wave's lanes (all 64 lanes call it)
+DEV u64 wave_incl_scan64(u64 v) {
+  const u32 lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u32 lo = __shfl_up((u32)v, o, 64), hi = __shfl_up((u32)(v >> 32), o, 64);
+    if (lane >= (u32)o) v += (u64(hi) << 32) | lo;
+  }
+  return v;
+}
 // all 64 lanes must call these (wave-uniform control flow); one atomic per distinct index
 DEV void wave_add_u32(u32* arr, u32 idx, u32 v, bool valid) {
   u64 pend = __ballot(valid);

@@ -190,6 +190,9 @@ class Engine {
     // persistence + recovery: restore batches reuse the import path (world == 1: own buffers)
     d_.persist = (u32)get("persist", 0);
     d_.limits = get("queue_limits", 0) ? 1u : 0u;   // x-max-length / x-overflow honoured (q_limit)
+    // x-max-length-bytes honoured (q_blimit, q_bytes, q_broom; the BL instantiations and k_byte_room)
+    d_.blimits = get("queue_limit_bytes", 0) ? 1u : 0u;
+    if (d_.blimits && !d_.limits) throw std::runtime_error("queue_limit_bytes needs queue_limits");
     d_.persist_max = d_.persist ? (u32)get("persist_max", d_.cmd_max) : 0;
     d_.persist_bytes = d_.persist ? get("persist_bytes", 64ull << 20) : 0;
     // restore / host-publish records at world 1: recovery batches (persist) and messages
@@ -504,6 +507,11 @@ class Engine {
     d_.ring_top = (u64*)dev("ring_top", 8);
     d_.q_max_cap = (u64*)dev("q_max_cap", 8ull * d_.q_max);
     d_.q_limit = (u32*)dev("q_limit", 4ull * d_.q_max);
+    if (d_.blimits) {
+      d_.q_blimit = (u64*)dev("q_blimit", 8ull * d_.q_max);
+      d_.q_bytes = (u64*)dev("q_bytes", 8ull * d_.q_max);
+      d_.q_broom = (u32*)dev("q_broom", 4ull * d_.q_max);
+    }
     if (d_.dlx) {
       dl_h_.q_dlx = (u32*)dev("q_dlx", 4ull * d_.q_max);
       dl_h_.q_dl_len = (u32*)dev("q_dl_len", 4ull * d_.q_max);
@@ -1014,6 +1022,7 @@ class Engine {
     o["egress_tail_engine"] = engine_no(copy_mode_ == 3, (u32)tail_engine_);
     o["h2d_split_min"] = h2d_split_min_;
     o["queue_limits"] = d_.limits;
+    o["queue_limit_bytes"] = d_.blimits;
     o["dead_letter"] = d_.dlx; o["dead_max"] = dl_h_.dead_max; o["dead_bytes"] = dl_h_.dead_bytes; o["dead_room"] = dead_room_; o["x_death"] = dl_h_.xdeath;
     o["alternate_exchange"] = alt_ ? 1 : 0;
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
@@ -2554,8 +2563,13 @@ class Engine {
     if (q >= d_.q_max || chslot >= d_.c_max * d_.chpc) throw std::runtime_error("basic_get: bad queue / channel");
     Range rg("chanamq.basic_get");
     sync();
-    hipLaunchKernelGGL(k_basic_get, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms, get_out_dev_,
-                       get_cap_, get_res_dev_, (u32)(seq_ ? seq_ - 1 : 0));   // (the last step submitted; before the first: 0)
+    const u32 last = (u32)(seq_ ? seq_ - 1 : 0);   // (the last step submitted; before the first: 0)
+    if (d_.blimits)
+      hipLaunchKernelGGL(k_basic_get<true>, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms,
+                         get_out_dev_, get_cap_, get_res_dev_, last);
+    else
+      hipLaunchKernelGGL(k_basic_get<false>, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms,
+                         get_out_dev_, get_cap_, get_res_dev_, last);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s_comp_));
     const GetRes& r = *get_res_h_;
@@ -2784,7 +2798,7 @@ class Engine {
     Range rg("chanamq.K7-K11.tail");
     u32 nch = d.c_max * d.chpc;
     const u32 pbits = d.q_bits + d.rank_bits;
-    if (pbits <= SORT_ONEPASS_BITS) {
+    if (pbits <= SORT_ONEPASS_BITS && !d.blimits) {
       // single-pass sort with the ring plan folded into the histogram's last block and the
       // enqueue into the scatter (k_rs_hist_plan / k_rs_scatter_enq): two launches
       const u32 nt = ceil_div(d.pair_max, SORT_TILE);
@@ -2800,8 +2814,18 @@ class Engine {
       u32* pv[2] = {d.pair_v[0], d.pair_v[1]};
       const u32 psrc = radix_sort(s, d, pk, pv, &d.tot[TS_PAIR_N], d.pair_max, pbits);
       hipLaunchKernelGGL(k_qfirst, blocks(d.pair_max, 256), dim3(256), 0, s, d, psrc);
-      hipLaunchKernelGGL(k_ring_plan, capped(ceil_div(d.pair_max, 256), 1024), dim3(256), 0, s, d, psrc);
-      hipLaunchKernelGGL(k_enqueue, capped(ceil_div(d.pair_max, 256), 1024), dim3(256), 0, s, d, psrc);
+      // byte limits on (DS.blimits): this path at every key width -- k_byte_room needs the sorted pair
+      // arrays, which the fused path never materialises -- with K_q computed ahead of the ring plan
+      // and the BL instantiations of the plan and the enqueue
+      const dim3 pg = capped(ceil_div(d.pair_max, 256), 1024);
+      if (d.blimits) {
+        hipLaunchKernelGGL(k_byte_room, pg, dim3(256), 0, s, d, psrc);
+        hipLaunchKernelGGL(k_ring_plan<true>, pg, dim3(256), 0, s, d, psrc);
+        hipLaunchKernelGGL(k_enqueue<true>, pg, dim3(256), 0, s, d, psrc);
+      } else {
+        hipLaunchKernelGGL(k_ring_plan<false>, pg, dim3(256), 0, s, d, psrc);
+        hipLaunchKernelGGL(k_enqueue<false>, pg, dim3(256), 0, s, d, psrc);
+      }
     }
     // without persistence nothing runs after k_post: it also writes the host-visible
     // outputs and its last block the counters (fused k_host_out)
@@ -2816,7 +2840,9 @@ class Engine {
     else hipLaunchKernelGGL(k_chan_advance<false>, capped(nch, 1024), dim3(256), 0, s, d);
     // k_dequeue first puts requeued deliveries back in front of their queues' heads, in
     // queue-offset order (QueueEntity.scala:415-446), then dispatches
-    if (d.dlx) hipLaunchKernelGGL(k_dequeue<true>, dim3(d.q_max), dim3(256), 0, s, d);
+    if (d.blimits && d.dlx) hipLaunchKernelGGL((k_dequeue<true, true>), dim3(d.q_max), dim3(256), 0, s, d);
+    else if (d.blimits) hipLaunchKernelGGL((k_dequeue<false, true>), dim3(d.q_max), dim3(256), 0, s, d);
+    else if (d.dlx) hipLaunchKernelGGL(k_dequeue<true>, dim3(d.q_max), dim3(256), 0, s, d);
     else hipLaunchKernelGGL(k_dequeue<false>, dim3(d.q_max), dim3(256), 0, s, d);   // (its last block lays out the runs)
     hipLaunchKernelGGL(k_dv_write, blocks(d.deliv_max, 256), dim3(256), 0, s, d);
     if (d.c_max <= CONN_LAYOUT_MAX) {
