@@ -507,6 +507,10 @@ class GpuDataPlane(ControlState):
         self._up_at("q_ttl", q.ttl_ms, q.slot, np.int64)
         if self.queue_limit_bytes:   # (an empty ring holds no bytes: zeroed with the head)
             self._up_at("q_bytes", 0, q.slot, np.uint64)
+        if self.info.get("spill_bytes"):   # (nothing of a new queue is tiered: not the slot's last tenant's hold)
+            self._up_at("q_cold_lim", (1 << 64) - 1, q.slot, np.uint64)
+            self._up_at("q_spill_cur", 0, q.slot, np.uint64)
+            self._up_at("q_cold_cur", 0, q.slot, np.uint64)
         if self.queue_limits:
             self.queue_limit_changed(q)
         if self.dead_letter:

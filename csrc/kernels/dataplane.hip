@@ -1426,7 +1426,7 @@ DEV void route_one(const DS& d, u32 p, u32 lane) {
                (8 + 12 + pb.props_len) /*header*/;
       u32 fm = d.conn_frame_max[pb.conn];
       u32 fmb = fm ? fm - 8 : 0xffffffffu;
-      u32 nb = pb.body_size ? (pb.body_size + fmb - 1) / fmb : 0;
+      u32 nb = pb.body_size ? (pb.body_size - 1) / fmb + 1 : 0;   // (no sum: fmb is 2^32 - 1 for frame-max 0)
       sz += pb.body_size + 8 * nb;
       atomicAdd(&d.conn_ret_bytes[pb.conn], sz);
       rsz = sz;
@@ -2837,7 +2837,7 @@ DEV u32 deliver_size(const DS& d, u32 cons, const MsgEnt& m, u32 conn) {
   u32 sz = 8 + mp + 8 + 12 + m.props_len;
   u32 fm = d.conn_frame_max[conn];
   u32 fmb = fm ? fm - 8 : 0xffffffffu;
-  u32 nb = m.body_len ? (m.body_len + fmb - 1) / fmb : 0;
+  u32 nb = m.body_len ? (m.body_len - 1) / fmb + 1 : 0;   // (no sum: fmb is 2^32 - 1 for frame-max 0)
   return sz + m.body_len + 8 * nb;
 }
 
@@ -2945,10 +2945,11 @@ struct DqCons { u32 c, ch, ok, noack, pc, glob, unacked; };
 // and only what would stay queued is bounded.  A trimmed entry goes the way of an expired one
 // (store record kind 1, release); a durable queue on a persisting plane draws on the TTL walk's
 // record budget, and the next steps trim what that did not cover.  The entries of the runs
-// written this step lie below `head` and are not touched.  q_spill_cur and q_cold_lim cope
-// with a head that passes them (spill_queue restarts at the head; k_dequeue, k_cold_scan and
-// k_cold_commit compare them with the head).  Stores q_head[q] if it moved; a dead-letter
-// exchange would take the trimmed entries here.
+// written this step lie below `head` and are not touched.  q_spill_cur copes with a
+// head that passes it (spill_queue restarts at the head); for q_cold_lim the rule is the one at
+// DS.q_cold_lim (dp_state.h): a trim without a dead-letter exchange may leave head > q_cold_lim
+// until the next step's cold_lim_rescan puts the limit at the first cold entry again, or at ~0.
+// Stores q_head[q] if it moved; a dead-letter exchange would take the trimmed entries here.
 // BL (x-max-length-bytes): `bytes` are the queue's ready bytes at `head`; the trim also runs while
 // they exceed the byte limit B.  An iteration looks at the (up to) 64 entries at the head, their
 // body sizes loaded together: with E_i the exclusive prefix of the sizes, entry i leaves iff
@@ -3019,6 +3020,30 @@ DEV void trim_head(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc*
   }
   if (lane == 0) d.q_head[q] = head;
   if (BL && lane == 0) d.q_bytes[q] = bytes;
+}
+// q_cold_lim once the head has reached it (wave 0 of the queue's block): the first cold entry
+// from the head on, ~0 when there is none -- the rule stated at DS.q_cold_lim.  A head that
+// stands at the first cold entry costs one look at that entry; a head that passed the limit
+// (TTL walk, purge, Basic.Get, trim) or a limit k_cold_in left in front of resident
+// entries is found here instead of holding the queue until some later k_cold_scan.
+// Returns the limit that holds now.
+DEV u64 cold_lim_rescan(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const Desc* ring) {
+  const u64 lim = d.q_cold_lim[q];
+  if (lim == ~0ull || head < lim) return lim;   // wave-uniform
+  const u32 lane = lane_id();
+  u64 first = ~0ull;
+  for (u64 b = head; b < tail; b += 64) {
+    const u64 i = b + lane;
+    bool cold = false;
+    if (i < tail) {
+      const u32 msg = ring[i & mask].msg;
+      cold = msg != INVALID && msg < d.msg_max && (d.msgs[msg].log_off & COLD_BIT) != 0;
+    }
+    const u64 cm = __ballot(cold);
+    if (cm) { first = b + (u64)(__ffsll((unsigned long long)cm) - 1); break; }
+  }
+  if (lane == 0 && first != lim) d.q_cold_lim[q] = first;
+  return first;
 }
 template <bool DLX, bool BL>
 DEV bool dequeue_queue(const DS& d) {
@@ -3103,8 +3128,9 @@ DEV bool dequeue_queue(const DS& d) {
     // (dead_leave) as far as it has room, and the walk ends at the first position whose body
     // may be cold (k_dead_pack could not copy it; k_cold_scan pages the head window back in)
     const u32 dx = DLX ? d.dl->q_dlx[q] : 0u;   // wave-uniform
+    const u64 clim0 = d.spill_bytes ? cold_lim_rescan(d, q, head, tail, mask, ring) : ~0ull;
     u64 wend = tail;
-    if (dx && d.q_cold_lim[q] < wend) wend = d.q_cold_lim[q];
+    if (dx && clim0 < wend) wend = clim0;
     // BL: the ready bytes before the walk (agent scope, like the head: the requeue above added to them)
     u64 qb = 0;
     if (BL) qb = __hip_atomic_load(&d.q_bytes[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3139,6 +3165,7 @@ DEV bool dequeue_queue(const DS& d) {
       head += nexp;
       if (live || full) break;
     }
+    if (d.spill_bytes) cold_lim_rescan(d, q, head, tail, mask, ring);   // (the walk may have passed it)
     if (lane == 0) { s_head = head; s_bytes = 0; }
     if (BL && lane == 0) s_qb = qb;
   } else if (!nodisp && tid - 64 < RUNS_PER_Q) {   // the consumers' inputs, beside the TTL walk
@@ -4332,7 +4359,7 @@ __global__ __launch_bounds__(64) void k_basic_get(DS d, u32 q, u32 ch, u32 noack
   u32 mp = 4 + 8 + 1 + 1 + m.ex_len + 1 + m.rk_len + 4;
   u32 fm = d.conn_frame_max[conn];
   u32 fmb = fm ? fm - 8 : 0xffffffffu;
-  u32 nb = m.body_len ? (m.body_len + fmb - 1) / fmb : 0;
+  u32 nb = m.body_len ? (m.body_len - 1) / fmb + 1 : 0;   // (no sum: fmb is 2^32 - 1 for frame-max 0)
   u64 need = 8ull + mp + 8 + 12 + m.props_len + m.body_len + 8ull * nb;
   u32 st = need > out_cap ? GET_NO_SPACE : (d.ch_win[ch] >= ucap ? GET_WINDOW_FULL : GET_OK);
   if (st != GET_OK) {
@@ -4427,6 +4454,19 @@ DEV bool spill_reserve(const DS& d, u32 sz, u64* pos) {
     if (prev == cur) { *pos = h; return true; }
     cur = prev;
   }
+}
+
+// the tail spill_reserve is full against, and whether `sz` bytes fit a ring whose head is `head`
+// (k_cold_scan sizes a wave's reservation with them before it makes it)
+DEV u64 spill_lagged_tail(const DS& d) {
+  u64 tail = *d.spill_tail;
+  for (u32 k = 0; k < SPILL_LAG; ++k) tail = d.spill_tail_lag[k] < tail ? d.spill_tail_lag[k] : tail;
+  return tail;
+}
+DEV bool spill_fits(const DS& d, u64 head, u64 tail, u32 sz) {
+  const u64 phys = head % d.spill_bytes;
+  if (phys + sz > d.spill_bytes) head += d.spill_bytes - phys;
+  return head + sz - tail <= d.spill_bytes;
 }
 
 // Cold bodies to host memory (host-driven, between steps, when the HBM log fills): one
@@ -4543,6 +4583,7 @@ __global__ __launch_bounds__(64) void k_cold_scan(DS d, u32 window, ColdRec* out
   const Desc* ring = d.ring + d.q_ring_off[q];
   const u64 start = lim > head ? lim : head;
   const u64 stop = tail < head + window ? tail : head + window;
+  __shared__ u32 s_incl[64];
   u64 end = start;
   for (u64 b = start; b < stop; b += 64) {
     const u64 i = b + lane;
@@ -4557,38 +4598,59 @@ __global__ __launch_bounds__(64) void k_cold_scan(DS d, u32 window, ColdRec* out
         cold = (lo & COLD_BIT) != 0;
       }
     }
-    // one ring reservation for the wave's cold bodies, in lane order
+    // one ring reservation for the wave's cold bodies, in lane order: all of them, or the
+    // longest prefix that the ring and the batch have room for (all-or-nothing could never
+    // page in 64 cold bodies that together exceed the ring's free room: the queue stood still)
     u32 off = cold ? sz : 0;
     for (int o = 1; o < 64; o <<= 1) {
       const u32 y = __shfl_up(off, o, 64);
       if (lane >= (u32)o) off += y;
     }
-    const u32 total = __shfl(off, 63, 64);
-    off -= cold ? sz : 0;
-    u64 pos = 0;
-    u32 ok = 1, k0 = 0;
     const u64 cm = __ballot(cold);
     const u32 nc = (u32)__popcll(cm);
+    const u32 rank = (u32)__popcll(cm & lanemask_lt());   // this lane's place among the cold ones
+    if (cold) s_incl[rank] = off;   // bytes of the first rank + 1 cold bodies
+    off -= cold ? sz : 0;
+    __syncthreads();   // (the block is this one wave; b and stop are uniform)
+    u64 pos = 0;
+    u32 nok = 0, k0 = 0;
     if (lane == 0 && nc) {
       k0 = atomicAdd(n_out, nc);
-      ok = k0 + nc <= max_n && spill_reserve(d, total, &pos) ? 1u : 0u;
+      nok = k0 < max_n ? (max_n - k0 < nc ? max_n - k0 : nc) : 0u;
+      // the longest prefix the ring has room for now: room only shrinks with the size (the pad to
+      // the wrap included), so a bisection over the prefix sums with the ring read once; another
+      // queue's block may take room meanwhile, then the reservation steps down
+      const u64 h0 = __hip_atomic_load(d.spill_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const u64 t0 = spill_lagged_tail(d);
+      u32 fit = 0, over = nok + 1;   // fit bodies fit, over do not
+      while (over - fit > 1) {
+        const u32 mid = fit + (over - fit) / 2;
+        if (spill_fits(d, h0, t0, s_incl[mid - 1])) fit = mid; else over = mid;
+      }
+      nok = fit;
+      while (nok && !spill_reserve(d, s_incl[nok - 1], &pos)) --nok;
     }
-    ok = (u32)__shfl((int)ok, 0);
+    nok = (u32)__shfl((int)nok, 0);
     pos = shfl64(pos, 0);
     k0 = (u32)__shfl((int)k0, 0);
-    const u32 k = k0 + (u32)__popcll(cm & lanemask_lt());
+    const u32 k = k0 + rank;
+    const bool ok = cold && rank < nok;
     // the reserved bytes count as live from here: steps that run before k_cold_in (the
     // cold thread reads the store meanwhile) must not move the ring's tail over them
-    if (cold && ok) atomicAdd((unsigned long long*)&d.spill_live[((pos + off) / d.log_block) % d.n_spill_blocks],
-                              (unsigned long long)sz);
+    if (ok) atomicAdd((unsigned long long*)&d.spill_live[((pos + off) / d.log_block) % d.n_spill_blocks],
+                      (unsigned long long)sz);
     if (cold && k < max_n) {   // (not ok: a record of bytes 0, skipped by the host)
       ColdRec r;
-      r.msg = ok ? msg : INVALID; r.q = q; r.qpos = i; r.pos = pos + off; r.cold = lo & ~COLD_BIT;
+      r.msg = ok ? msg : INVALID; r.q = q; r.qpos = i; r.pos = ok ? pos + off : 0; r.cold = lo & ~COLD_BIT;
       r.bytes = ok ? sz : 0; r.pad = 0;
       out[k] = r;
     }
-    if (!ok) break;   // ring (or the batch) full: the rest waits for the next call
+    if (nok < nc) {   // ring (or the batch) full: the scan ends at the first entry left out
+      end = b + (u64)(__ffsll((unsigned long long)(cm & ~__ballot(ok))) - 1);
+      break;
+    }
     end = b + 64 < stop ? b + 64 : stop;
+    __syncthreads();   // lane 0 has read s_incl before the next wave of entries overwrites it
   }
   if (lane == 0) scan_end[q] = end == tail ? ~0ull : end;
 }
@@ -4784,6 +4846,12 @@ DEV void requeue_queue(const DS& d, u32 q, u64* kpos, u32* kidx, u32* cnt_p) {
   if (tid == 0) {
     d.q_head[q] = head - done;
     d.req_q_n[q] -= done;
+    // the tier cursors say "everything before me is tiered": the entries that came back in
+    // front of them are not (unacked deliveries stay where they are), so the walks restart there
+    if (done && d.spill_bytes) {
+      if (d.q_spill_cur[q] > head - done) d.q_spill_cur[q] = head - done;
+      if (d.q_cold_cur[q] > head - done) d.q_cold_cur[q] = head - done;
+    }
   }
 }
 

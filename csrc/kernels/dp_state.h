@@ -270,7 +270,14 @@ struct DS {
   u64* spill_tail_lag;      // [SPILL_LAG]
   i64* spill_live;          // live bytes per spill block
   i64* cold_live;           // [COLD_SEGS] live bytes per cold-store segment (host unlinks freed ones)
-  u64* q_cold_lim;          // [q_max] deliveries stop here (~0: nothing of the queue is cold)
+  // q_cold_lim: no entry of the queue before this position is cold, and deliveries, the dead-letter
+  // TTL walk and trim stop here (~0: nothing of the queue is cold).  k_cold_commit lowers it to the
+  // lowest position it turned cold; k_cold_in moves it to the first entry its scan left out.  A head
+  // that reaches it without finding a cold entry there (or passes it: TTL walk, purge, Basic.Get)
+  // makes k_dequeue look for the first cold entry from the head on and store that, or ~0
+  // (cold_lim_rescan), so a stale limit never holds a queue.  A queue declared into the slot starts
+  // at ~0 with both cursors at 0 (GpuDataPlane.queue_declared)
+  u64* q_cold_lim;          // [q_max]
   u64* q_spill_cur;         // [q_max] spill_queue resumes here: entries before it are tiered
   u64* q_cold_cur;          // [q_max] k_cold_pick resumes here: entries before it are cold
   u64* id_next;             // snowflake virtual sequence position
