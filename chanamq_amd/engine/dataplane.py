@@ -17,6 +17,7 @@ import numpy as np
 
 from .. import ops
 from ..protocol import constants as C
+from . import prio
 from .control import ControlError, ControlState
 from .layout import (CONN_OUT, CONSUMED_REC, EGRESS_REF, RING_MOVE, CTRL_REC, CTRL_DGET, CTRL_TXBUF, INVALID, MF_HAS_TS,
                      MF_HOSTPUB, MF_PERSIST,
@@ -73,8 +74,15 @@ class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
                  world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
                  headers_match=False, queue_limits=False, dead_letter=False, x_death=False,
-                 alternate_exchange=False, queue_limit_bytes=False, **cfg):
-        """``queue_limit_bytes`` (needs ``queue_limits``): queues honour x-max-length-bytes under
+                 alternate_exchange=False, queue_limit_bytes=False, priority_queues=False, **cfg):
+        """``priority_queues``: queues honour x-max-priority: a queue declared with P takes P + 1
+        consecutive slots, its lanes (q_prio / q_lane_base); k_prio_lane moves each routed pair to
+        the lane of its publish's priority ahead of the sort, and k_prio_dispatch, behind the PRIO
+        instantiation of k_dequeue, serves the base slot's consumers and Gets from the lanes in
+        order.  Off: the argument is ignored and the step launches what it launched before.
+        Single-rank planes only.
+
+        ``queue_limit_bytes`` (needs ``queue_limits``): queues honour x-max-length-bytes under
         their x-overflow mode (q_blimit; the device keeps every queue's ready bytes in q_bytes:
         k_byte_room and the BL instantiations of k_ring_plan / k_enqueue / k_dequeue / k_basic_get;
         the step sorts its pairs on the materialised path at every key width).  Off: the argument
@@ -116,6 +124,8 @@ class GpuDataPlane(ControlState):
             raise ValueError("x_death=True needs dead_letter=True")
         if queue_limit_bytes and not queue_limits:
             raise ValueError("queue_limit_bytes=True needs queue_limits=True")
+        if priority_queues and world > 1:
+            raise ValueError("priority_queues=True is not served on a sharded plane (world > 1)")
         self.mod = ops.load()
         full = dict(cfg)
         full.setdefault("egress_ref_back", -1 if egress_ref is None else int(egress_ref))
@@ -138,6 +148,8 @@ class GpuDataPlane(ControlState):
                     alternate_exchange=int(bool(alternate_exchange)))
         if queue_limit_bytes:   # (off: the engine's cfg is what it was)
             full.update(queue_limit_bytes=1)
+        if priority_queues:
+            full.update(priority_queues=1)
         self.eng = self.mod.Engine(full)
         self.info = self.eng.info()
         sz = self.info["sizeof"]
@@ -194,7 +206,11 @@ class GpuDataPlane(ControlState):
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
                          shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits,
                          dead_letter=dead_letter, x_death=x_death, alternate_exchange=alternate_exchange,
-                         queue_limit_bytes=queue_limit_bytes)
+                         queue_limit_bytes=queue_limit_bytes, priority_queues=priority_queues)
+        # (a durable priority queue is refused where a store takes the plane's records: control.py)
+        self.persist = bool(i.get("persist"))
+        if self.priority_queues:   # every slot is its own base until a priority queue takes it
+            self._up("q_lane_base", np.arange(self.q_max, dtype=np.uint32))
 
     # ================================================================== uploads
     # ``defer`` (set by the broker around control work done while steps keep running): table
@@ -515,6 +531,9 @@ class GpuDataPlane(ControlState):
             self.queue_limit_changed(q)
         if self.dead_letter:
             self.queue_dlx_changed(q)
+        if getattr(self, "priority_queues", False):   # (a lane behind the base: q_prio 0, its base slot)
+            self._up_at("q_prio", q.max_priority or 0, q.slot, np.uint32)
+            self._up_at("q_lane_base", q.lane_of if q.lane_of >= 0 else q.slot, q.slot, np.uint32)
         self._up_at("q_rr", 0, q.slot, np.uint32)
         self._up_at("req_q_n", 0, q.slot, np.uint32)
         self._up_at("q_active", 1, q.slot, np.uint32)
@@ -560,6 +579,9 @@ class GpuDataPlane(ControlState):
 
     def queue_deleted(self, q):
         self._up_at("q_active", 0, q.slot, np.uint32)
+        if self.priority_queues:
+            self._up_at("q_prio", 0, q.slot, np.uint32)
+            self._up_at("q_lane_base", q.slot, q.slot, np.uint32)
         if self.dead_letter:   # (a reject of one of its deliveries, still in a window, is then an ack)
             self._up_at("q_dlx", 0, q.slot, np.uint32)
         if self.defer:
@@ -675,7 +697,22 @@ class GpuDataPlane(ControlState):
     def basic_get(self, conn, ch, q, no_ack, now_ms=None):
         """Basic.Get between steps (k_basic_get): the head of queue slot ``q`` after the
         TTL skip, with the channel's next delivery tag.  Returns (GetOk + header + body
-        frames | None when empty, ready messages left).  Reference FrameStage.scala:1199-1229."""
+        frames | None when empty, ready messages left).  Reference FrameStage.scala:1199-1229.
+        A priority queue answers as it does within a step: from its highest lane that holds a
+        message, the count over all lanes (written into the rendered GetOk here)."""
+        slots = self.lane_slots(q)
+        if len(slots) == 1:
+            return self._basic_get_slot(conn, ch, q, no_ack, now_ms)
+        for s in slots:
+            more = sum(self._u64("q_tail", t) - self._u64("q_head", t) for t in slots if t != s)
+            frames, left = self._basic_get_slot(conn, ch, s, no_ack, now_ms)
+            if frames is not None:
+                return prio.patch_getok_count(frames, left + more), left + more
+            if left:   # held (a full dead list, a cold head)
+                return None, left + more
+        return None, 0
+
+    def _basic_get_slot(self, conn, ch, q, no_ack, now_ms=None):
         now = int(time.time() * 1000) if now_ms is None else int(now_ms)
         s = self.chslot(conn, ch)
         while True:
@@ -821,6 +858,13 @@ class GpuDataPlane(ControlState):
 
     def _cold_store(self, store, recs):
         recs = recs[recs["bytes"] > 0]
+        if self.priority_queues and len(recs):
+            # the cold store takes no body of a priority queue (its lanes are dispatched across their
+            # heads, which a cold limit would hold): what the pick found in lane slots is left out
+            # before anything is stored or committed
+            lanes = {s for s, lq in list(self.queue_by_slot.items()) if lq.lanes or lq.lane_of >= 0}   # (a copy: the control plane may declare meanwhile)
+            if lanes:
+                recs = recs[~np.isin(recs["q"], np.fromiter(lanes, np.uint32, len(lanes)))]
         if not len(recs):
             return None
         ring, sb = self._spill_view(), self.info["spill_bytes"]
@@ -914,13 +958,15 @@ class GpuDataPlane(ControlState):
 
     def message_count(self, q):
         """Ready messages of queue slot ``q`` (AMQP Queue.DeclareOk message-count)."""
-        return self._u64("q_tail", q) - self._u64("q_head", q)
+        return sum(self._u64("q_tail", s) - self._u64("q_head", s) for s in self.lane_slots(q))
 
     def queue_bytes(self, q):
         """Ready bytes of queue slot ``q`` (queue_limit_bytes on): the body bytes of its ready
         messages, as the device keeps them in q_bytes."""
         if not self.queue_limit_bytes:
             raise RuntimeError("queue_bytes() needs queue_limit_bytes=True")
+        if len(self.lane_slots(q)) > 1:   # (k_prio_dispatch keeps no byte count: such a queue has no byte limit)
+            raise RuntimeError("queue_bytes() is not kept for a priority queue")
         return self._u64("q_bytes", q)
 
     def queue_tail(self, q):
@@ -930,6 +976,9 @@ class GpuDataPlane(ControlState):
     def purge(self, q):
         """Queue.Purge: mark every ready entry expired; the next step's dequeue (K12 TTL
         skip) releases them and their body-log bytes.  Returns the purged count."""
+        return sum(self._purge_slot(s) for s in self.lane_slots(q))   # (a priority queue: every lane)
+
+    def _purge_slot(self, q):
         head, tail = self._u64("q_head", q), self._u64("q_tail", q)
         n = tail - head
         if n <= 0:

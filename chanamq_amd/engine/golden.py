@@ -14,7 +14,7 @@ import numpy as np
 
 from ..models.matcher import topic_match
 from ..protocol import constants as C
-from . import xdeath
+from . import prio, xdeath
 from .control import ControlState
 from .layout import (MF_HAS_TS, MF_PERSIST, RDESC, SS_CTRL, SS_FRAME_ERROR, SS_OVERFLOW, SS_TOO_LARGE,
                      SS_UNEXPECTED)
@@ -157,7 +157,8 @@ class GoldenDataPlane(ControlState):
         return tot
 
     def message_count(self, q):
-        return len(self.ring[q])
+        """Ready messages of queue slot ``q`` (a priority queue: over all its lanes)."""
+        return sum(len(self.ring[s]) for s in self.lane_slots(q))
 
     def queue_bytes(self, q):
         """Ready bytes of queue slot ``q``: the body bytes of its ring entries, summed over the ring
@@ -169,9 +170,12 @@ class GoldenDataPlane(ControlState):
         return qq.max_length_bytes if self.queue_limit_bytes else None
 
     def purge(self, q):
-        ring = self.ring[q]
-        self.ring[q] = [(m, red, 1) for (m, red, _) in ring]   # released by the next dequeue
-        return len(ring)
+        n = 0
+        for s in self.lane_slots(q):   # (a priority queue: every lane)
+            ring = self.ring[s]
+            self.ring[s] = [(m, red, 1) for (m, red, _) in ring]   # released by the next dequeue
+            n += len(ring)
+        return n
 
     def recover(self, conn, ch):
         s = self.chslot(conn, ch)
@@ -308,7 +312,22 @@ class GoldenDataPlane(ControlState):
             self._release(m)
 
     def basic_get(self, conn, ch, q, no_ack, now_ms=0):
-        """Basic.Get between steps: spec of k_basic_get (dataplane.hip)."""
+        """Basic.Get between steps.  A priority queue answers as it does within a step: from its
+        highest lane that holds a message once that lane's expired head is gone, with the count over
+        all lanes (the lanes below keep their expired heads until a step walks them)."""
+        slots = self.lane_slots(q)
+        if len(slots) == 1:
+            return self._basic_get_slot(conn, ch, q, no_ack, now_ms)
+        for s in slots:
+            more = sum(len(self.ring[t]) for t in slots if t != s)
+            frames, left = self._basic_get_slot(conn, ch, s, no_ack, now_ms, more)
+            if frames is not None or left:   # answered, or held by a full dead list
+                return frames, left + more
+        return None, 0
+
+    def _basic_get_slot(self, conn, ch, q, no_ack, now_ms=0, more=0):
+        """Basic.Get of one slot: spec of k_basic_get (dataplane.hip).  ``more``: what the other lanes
+        of a priority queue hold, added to the GetOk's message-count."""
         ring = self.ring[q]
         dx = self._dx(q)
         while ring and ring[0][2] and ring[0][2] <= now_ms:
@@ -343,7 +362,7 @@ class GoldenDataPlane(ControlState):
         self._mark_dirty(s)
         fm = self.conns[conn].frame_max
         mp = (struct.pack(">HHQB", 60, 71, tag, 1 if red else 0) + bytes([len(msg.ex)]) + msg.ex
-              + bytes([len(msg.rk)]) + msg.rk + struct.pack(">I", len(ring)))
+              + bytes([len(msg.rk)]) + msg.rk + struct.pack(">I", len(ring) + more))
         parts = [_frame(1, st["num"], mp), _frame(2, st["num"], struct.pack(">HHQ", 60, 0, len(msg.body)) + msg.props)]
         step = fm - 8 if fm else len(msg.body)
         for i in range(0, len(msg.body), max(step, 1)):
@@ -789,7 +808,13 @@ class GoldenDataPlane(ControlState):
             gets[g["q"]].append(g)
         gempty = defaultdict(list)
         for q in sorted(self.queue_by_slot):
-            delivs.extend(self._dequeue(q, now_ms, budget, gets.get(q, ()), gempty, out))
+            qq = self.queue_by_slot[q]
+            if qq.lane_of >= 0:     # a priority queue's lane: served at its base slot
+                continue
+            if qq.lanes:
+                delivs.extend(self._dequeue_prio(qq, now_ms, budget, gets.get(q, ()), gempty, out))
+            else:
+                delivs.extend(self._dequeue(q, now_ms, budget, gets.get(q, ()), gempty, out))
         # ---- tags: stable sort by chslot
         delivs.sort(key=lambda d: d["chslot"])
         for d in delivs:
@@ -920,6 +945,9 @@ class GoldenDataPlane(ControlState):
         cnt = self.counters
         for q in qs:
             qq = self.queue_by_slot[q]
+            if qq.lanes:   # a priority queue (k_prio_lane): the pair moves to the lane of the message's priority
+                qq = qq.lanes[prio.lane_of(prio.prio_of_props(msg.props), qq.max_priority)]
+                q = qq.slot
             ring = self.ring[q]
             # x-max-length-bytes, reject-publish (k_byte_room): pair r of the queue's pairs of the step
             # passes iff Y + E_r < B -- Y the ready bytes when the step's enqueue began, E_r the body
@@ -1009,7 +1037,105 @@ class GoldenDataPlane(ControlState):
             return now_ms + int(e)
         return 0
 
-    def _dequeue(self, q, now_ms, budget, gets=(), gempty=None, step_out=None):
+    def _dequeue_prio(self, base, now_ms, budget, gets, gempty, step_out):
+        """A priority queue's step (k_dequeue<.., PRIO> + k_prio_dispatch): every lane takes the TTL
+        walk as a queue without consumers, then the base slot's Gets and consumers are served from V,
+        the lanes' ready entries in lane order, by the rules of ``_dequeue``.  A grant is a piece of
+        V and becomes one run per lane it touches; a channel's deliveries come out in lane order
+        (runs_body orders by run slot), then in the order the runs were written."""
+        slots = [lq.slot for lq in base.lanes]
+        for s in slots:
+            self._dequeue(s, now_ms, budget, walk_only=True)
+        rings = [self.ring[s] for s in slots]
+        runs = [[] for _ in slots]    # per lane: its deliveries in run order
+        took = [0] * len(slots)       # entries handed out from each lane's front
+
+        def entry(lane, k, **kw):
+            s = slots[lane]
+            msg, red, exp = rings[lane][k]
+            return dict(msg=msg, q=s, qpos=self.qpos_head[s] + k, expire=exp, redelivered=red, **kw)
+
+        ngot = 0
+        for g in gets:
+            s = g["chslot"]
+            st = self.ch[s]
+            left = sum(len(r) for r in rings) - sum(took)
+            if not left:
+                gempty[g["conn"]].append(st["num"])
+                continue
+            if st["win"] >= self.ucap or ngot >= 32:   # (RUNS_PER_Q / 2 Get runs per queue)
+                step_out["ctrl"].append((g["conn"], g["raw"], True))
+                continue
+            lane = next(l for l, r in enumerate(rings) if len(r) > took[l])
+            st["win"] += 1
+            if not g["noack"]:
+                st["unacked"] += 1
+                self.cons_unacked[-1] += 1
+            runs[lane].append(entry(lane, took[lane], chslot=s, cons=-1, noack=g["noack"], get_left=left - 1))
+            took[lane] += 1
+            ngot += 1
+        counts = [len(r) - t for r, t in zip(rings, took)]
+        remaining = n_v = sum(counts)
+        mall = len(base.consumers)
+        if mall and n_v:
+            def v_entry(off):
+                lane, pos, _ = prio.split_piece(counts, off, 1)[0]
+                return rings[lane][took[lane] + pos]
+            m = min(mall, 64 - ngot)
+            r = self.qrr[base.slot] % mall
+            grants = []
+            for j in range(m):
+                cid = base.consumers[(r + j) % mall]
+                c = self.consumers[cid]
+                chan = self.conns[c.conn].channels[c.ch]
+                st = self.ch[self.chslot(c.conn, c.ch)]
+                g = 0
+                if remaining and c.active and chan.flow:
+                    share = -(-remaining // (m - j))
+                    want = min(share, self.deliver_cap)
+                    cap = self.deliver_cap_bytes
+                    if cap and want > 1:
+                        s0 = self._deliver_size(c, v_entry(n_v - remaining)[0])
+                        want = min(want, 1 if s0 >= cap else cap // s0)
+                    pc = chan.prefetch_count
+                    if not c.no_ack and pc and not chan.global_:
+                        want = min(want, max(pc - self.cons_unacked[cid], 0))
+                    g = min(want, self.ucap - st["win"])
+                    st["win"] += g
+                    if not c.no_ack and pc and chan.global_ and g:
+                        g2 = min(g, max(pc - st["unacked"], 0))
+                        st["win"] -= g - g2
+                        st["unacked"] += g2
+                        g = g2
+                    elif not c.no_ack and g:
+                        st["unacked"] += g
+                    if not c.no_ack and g:
+                        self.cons_unacked[cid] += g
+                grants.append((cid, g))
+                remaining -= g
+            base_took = list(took)
+            off = 0
+            for cid, g in grants:
+                if not g:
+                    continue
+                c = self.consumers[cid]
+                chan_s = self.chslot(c.conn, c.ch)
+                for lane, pos, n in prio.split_piece(counts, off, g):
+                    for k in range(n):
+                        runs[lane].append(entry(lane, base_took[lane] + pos + k, chslot=chan_s, cons=cid,
+                                                noack=c.no_ack, tag_str=c.tag.encode()))
+                off += g
+            for lane, pos, n in prio.split_piece(counts, 0, off):
+                took[lane] += n
+            self.qrr[base.slot] = (r + 1) % mall
+        out = []
+        for lane, s in enumerate(slots):
+            out.extend(runs[lane])
+            del rings[lane][:took[lane]]
+            self.qpos_head[s] += took[lane]
+        return out
+
+    def _dequeue(self, q, now_ms, budget, gets=(), gempty=None, step_out=None, walk_only=False):
         qq = self.queue_by_slot[q]
         ring = self.ring[q]
         cnt = self.counters
@@ -1040,6 +1166,8 @@ class GoldenDataPlane(ControlState):
             ring.pop(0)
             self.qpos_head[q] += 1
             cnt["n_expired"] += 1
+        if walk_only:   # a priority queue's lane: dispatched by _dequeue_prio
+            return []
         # the step's Basic.Gets of this queue, in wire order, ahead of its consumers (spec of
         # k_dequeue's request loop): GetOk as a delivery on the getter's channel, GetEmpty at
         # the end of its connection's egress, a full delivery window -> the host serves it

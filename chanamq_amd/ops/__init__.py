@@ -18,7 +18,8 @@ _SRC = os.path.join(_ROOT, "csrc", "kernels")
 _EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 EXT_PATH = os.path.join(_HERE, "_dataplane" + _EXT)
 SOURCES = ["engine.hip", "dataplane.hip", "dp_state.h", "dp_common.h", "step_abi.h", "delta_stage.h", "xchg_host.h",
-           "xchg_rccl.h", "dp_util.h", "dp_frame_scan.h", "dp_headers.h", "dp_xdeath.h", "xdeath_plan.h", "sdma_plan.h", "xchg_worker.h", "side_box.h"]
+           "xchg_rccl.h", "dp_util.h", "dp_frame_scan.h", "dp_headers.h", "dp_xdeath.h", "xdeath_plan.h", "sdma_plan.h", "xchg_worker.h", "side_box.h",
+           "dp_prio.h", "prio_plan.h"]
 
 
 def _src_hash():

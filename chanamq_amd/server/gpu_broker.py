@@ -220,7 +220,8 @@ class GpuBroker:
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
                  persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False,
-                 dead_letter=False, x_death=False, alternate_exchange=False, queue_limit_bytes=False):
+                 dead_letter=False, x_death=False, alternate_exchange=False, queue_limit_bytes=False,
+                 priority_queues=False):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -250,6 +251,14 @@ class GpuBroker:
             raise ValueError("queue_limit_bytes=True needs queue_limits=True")
         if self.queue_limit_bytes and not getattr(plane, "queue_limit_bytes", False):
             raise ValueError("queue_limit_bytes=True needs a data plane built with queue_limit_bytes=True")
+        # priority queues (chana.mq.gpu.priority-queues): Queue.Declare's x-max-priority is parsed and
+        # passed to the plane (built with priority_queues=True, which serves it); off, it is ignored
+        # as always before.  Single node only
+        self.priority_queues = bool(priority_queues)
+        if self.priority_queues and not getattr(plane, "priority_queues", False):
+            raise ValueError("priority_queues=True needs a data plane built with priority_queues=True")
+        if self.priority_queues and node is not None:
+            raise ValueError("priority_queues=True is not served on a sharded node")
         # dead-lettering (chana.mq.gpu.dead-letter): Queue.Declare's x-dead-letter-exchange /
         # x-dead-letter-routing-key are parsed and passed to the plane (built with dead_letter=True,
         # which serves them); off, they are ignored as always before.  Single node only
@@ -520,9 +529,13 @@ class GpuBroker:
             out = [{"vhost": q.vhost, "name": q.name, "durable": q.durable, "owner": q.owner,
                     "ready": self.plane.message_count(q.slot) if q.owner == self.plane.rank else None,
                     "consumers": len(q.consumers)} for q in self.plane.queues.values()]
+            if self.priority_queues:   # one row per queue (``ready`` is the sum over its priorities)
+                for row, q in zip(out, self.plane.queues.values()):
+                    row["max_priority"] = q.max_priority
             if self.queue_limit_bytes:   # the body bytes of the ready messages, beside their count
                 for row, q in zip(out, self.plane.queues.values()):
-                    row["ready_bytes"] = self.plane.queue_bytes(q.slot) if q.owner == self.plane.rank else None
+                    row["ready_bytes"] = self.plane.queue_bytes(q.slot) \
+                        if q.owner == self.plane.rank and q.max_priority is None else None
         return json.dumps(out)
 
     # ------------------------------------------------------------------ pipelined native loop
@@ -607,6 +620,8 @@ class GpuBroker:
         pc = self.plane.conns.get(c.id)
         if m.passive or pc is None or (m.queue and (pc.vhost, m.queue) in self.plane.queues):
             return False   # (an existing queue's DeclareOk needs its message count: a device read)
+        if self.priority_queues and "x-max-priority" in (m.arguments or {}):
+            return False   # (P + 1 slots' rows: more than a light section's delta records need hold)
         cap = 1
         while cap < self.plane.default_queue_capacity:
             cap <<= 1
@@ -1571,6 +1586,23 @@ class GpuBroker:
             return {}
         return dict(dead_letter_exchange=ex, dead_letter_routing_key=key)
 
+    def _prio_args(self, m, durable):
+        """Queue.Declare's x-max-priority as a ``declare_queue`` keyword, with priority-queues on ({}
+        with it off, or without the argument: ignored as always before).  Any AMQP integer type; a
+        value outside 1 .. PRIO_MAX, or one on a durable queue of a broker with a store, is 406
+        PRECONDITION_FAILED with nothing changed.  ``declare_queue`` refuses a value that differs
+        from the existing queue's and the argument beside a length limit."""
+        args = m.arguments or {}
+        if not self.priority_queues or "x-max-priority" not in args:
+            return {}
+        v = args["x-max-priority"]
+        v = v.value if isinstance(v, Typed) and v.tag in "bBsuIil" else v
+        P = self.plane.check_priority(v)
+        if durable and self.persistence is not None and not m.passive:
+            raise ControlError(C.PRECONDITION_FAILED, "x-max-priority is not served on a durable queue of a broker "
+                               "with a store", 50, 10)
+        return dict(max_priority=P)
+
     def _limit_args(self, m, q=None):
         """Queue.Declare's x-max-length / x-overflow as ``declare_queue`` keywords, with
         queue-limits on ({} with it off, or without a limit: the arguments are ignored as always
@@ -1740,7 +1772,7 @@ class GpuBroker:
                 raise ControlError(C.RESOURCE_LOCKED, f"queue '{name}' is exclusive to another connection", 50, 10)
             slot = p.declare_queue(vh, name, durable=m.durable, exclusive_owner=c.id if m.exclusive else -1,
                                    auto_delete=m.auto_delete, ttl_ms=ttl, passive=m.passive, **self._limit_args(m),
-                                   **self._dlx_args(m))
+                                   **self._dlx_args(m), **self._prio_args(m, m.durable))
             c.last_queue[ch] = name
             if self.persistence is not None and q is None and not m.passive:
                 self.persistence.queue(p.queue_by_slot[slot])

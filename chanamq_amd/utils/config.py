@@ -298,6 +298,10 @@ class Config:
             if not queue_limits:
                 raise ValueError("chana.mq.gpu.queue-limit-bytes needs chana.mq.gpu.queue-limits")
             plane.update(queue_limit_bytes=True)
+        # queues honour Queue.Declare's x-max-priority (off: the argument is ignored).  Single node only
+        priority_queues = bool(g(k + "priority-queues", False))
+        if priority_queues:
+            plane.update(priority_queues=True)
         # queues honour Queue.Declare's x-dead-letter-exchange / x-dead-letter-routing-key (off: ignored)
         dead_letter = bool(g(k + "dead-letter", False))
         if dead_letter:
@@ -325,7 +329,7 @@ class Config:
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
                       headers_match=headers_match, queue_limits=queue_limits, dead_letter=dead_letter, x_death=x_death,
                       alternate_exchange=alternate_exchange, queue_limit_bytes=queue_limit_bytes,
-                      mem_high_watermark=hi, mem_low_watermark=lo)
+                      priority_queues=priority_queues, mem_high_watermark=hi, mem_low_watermark=lo)
         return plane, broker
 
     def __repr__(self):

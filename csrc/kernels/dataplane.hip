@@ -1967,7 +1967,8 @@ DEV u32 dead_rec_size(const DS& d, const DeadItem& it, u32* lens, bool* cold, u3
 }
 // XD (DlState.xdeath): the sizes are k_dead_size's, phase 1 rewrites the property bytes and fills
 // the record's ban row (dp_xdeath.h); without it the kernel is the one it was
-template <bool XD>
+// PRIO (DS.prio, with XD): the ban row's entry for the source queue is its base slot
+template <bool XD, bool PRIO = false>
 __global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
   const u32 tid = threadIdx.x, lane = lane_id();
   if (phase == 0) {
@@ -2077,6 +2078,10 @@ __global__ __launch_bounds__(1024) void k_dead_pack(DS d, u32 phase, u32 room) {
         u32* ban_n = d.dl->dead_ban_n + ri;
         plen = xd_render(d, it, m, slot, dst + exl + rkl, d.dl->dead_plen[t], d.dl->dead_ban + (u64)ri * XD_ELEMS_MAX, ban_n, lane);
         bad = plen == INVALID;   // (the two passes disagree: never; the record then names no exchange and carries nothing)
+        // a dead letter of a priority queue's lane: routing emits base slots and the history's names
+        // resolve to base slots, so the source queue's own entry (xd_render: row[0]) is the base slot too
+        if (PRIO && !bad && it.reason != DL_REJECTED && lane == 0)
+          d.dl->dead_ban[(u64)ri * XD_ELEMS_MAX] = d.q_lane_base[it.q];
         if (bad) {
           plen = 0;
           if (lane == 0) *ban_n = 0;
@@ -3045,7 +3050,9 @@ DEV u64 cold_lim_rescan(const DS& d, u32 q, u64 head, u64 tail, u64 mask, const 
   if (lane == 0 && first != lim) d.q_cold_lim[q] = first;
   return first;
 }
-template <bool DLX, bool BL>
+// PRIO (DS.prio): a base slot of a priority queue (q_prio != 0) goes through as a queue without
+// consumers or Gets -- requeue, spill, TTL walk as for every lane -- and k_prio_dispatch serves it
+template <bool DLX, bool BL, bool PRIO>
 DEV bool dequeue_queue(const DS& d) {
   __shared__ u32 g_cons[RUNS_PER_Q];
   __shared__ u32 g_n[RUNS_PER_Q];
@@ -3098,6 +3105,8 @@ DEV bool dequeue_queue(const DS& d) {
     return false;
   }
   const bool nodisp = (d.in->flags & SF_NODISPATCH) != 0;
+  bool pbase = false;   // block-uniform
+  if (PRIO) pbase = d.q_prio[q] != 0;
   if (d.in->spill_frac && d.spill_bytes) {   // (kernel-uniform) the step's share of body tiering
     const u64 lim = *d.log_tail + (((u64)d.log_bytes * d.in->spill_frac) >> 16);
     spill_queue(d, q, lim, d.in->spill_hot, d.in->spill_budget, &d.ctr->spill_moved);
@@ -3169,7 +3178,7 @@ DEV bool dequeue_queue(const DS& d) {
     if (lane == 0) { s_head = head; s_bytes = 0; }
     if (BL && lane == 0) s_qb = qb;
   } else if (!nodisp && tid - 64 < RUNS_PER_Q) {   // the consumers' inputs, beside the TTL walk
-    const u32 j = tid - 64, mall0 = d.q_cons_n[q];
+    const u32 j = tid - 64, mall0 = pbase ? 0u : d.q_cons_n[q];
     if (j < mall0) {
       const u32 c = d.q_cons[d.q_cons_off[q] + (d.q_rr[q] % mall0 + j) % mall0];
       const u32 ch = d.cons_ch[c];
@@ -3196,7 +3205,7 @@ DEV bool dequeue_queue(const DS& d) {
   // rendered as GetOk + header + body by k_render; EMPTY / RETRY / WINDOW_FULL go back
   // to the host through the step's host-mapped GetOut (the host initialised them RETRY)
   u32 ngr = 0;
-  if (d.in->nget || ndg) {   // kernel-uniform
+  if ((d.in->nget || ndg) && !pbase) {   // kernel-uniform (pbase: block-uniform)
     if (tid == 0) {
       const u32 ng = d.in->nget < GET_STEP_MAX ? d.in->nget : GET_STEP_MAX;
       const u64 clim = d.q_cold_lim[q];   // a cold head waits for the host's page-in (RETRY)
@@ -3266,7 +3275,7 @@ DEV bool dequeue_queue(const DS& d) {
     head = s_head;
     ngr = s_ngr;
   }
-  const u32 mall = d.q_cons_n[q];
+  const u32 mall = pbase ? 0u : d.q_cons_n[q];
   // bodies from q_cold_lim on may be in the cold store: delivered once paged back in
   const u64 dlim = d.q_cold_lim[q] < tail ? d.q_cold_lim[q] : tail;
   const u64 avail = dlim > head ? dlim - head : 0;
@@ -3447,12 +3456,15 @@ DEV bool dequeue_queue(const DS& d) {
 // step's delivery runs (runs_body, once the kernel k_runs: a launch less per step)
 template <u32 NT> DEV void runs_body(const DS& d, u64* key_lds, u32 key_cap, u32* lds);
 #define DQ_RUN_LDS 2048   // runs that runs_body sorts in LDS (more: the global-memory sort)
-template <bool DLX, bool BL = false>
+// PRIO: no ticket and no runs_body here -- k_prio_dispatch, launched next, adds the priority queues'
+// runs and its last block lays out the step's
+template <bool DLX, bool BL = false, bool PRIO = false>
 __global__ __launch_bounds__(256) void k_dequeue(DS d) {
   __shared__ u64 key_lds[DQ_RUN_LDS];
   __shared__ u32 lds[256 / 64 + 1];
   __shared__ u32 s_last;
-  const bool wrote = dequeue_queue<DLX, BL>(d);
+  const bool wrote = dequeue_queue<DLX, BL, PRIO>(d);
+  if (PRIO) return;
   // every block's runs and counts reach the device-wide coherence point before its ticket
   // (agent scope: the last block may run on another XCD, whose L2 does not see this one's);
   // a block that wrote no runs stored its zero count agent-coherent and skips the L2
@@ -3543,6 +3555,8 @@ DEV void runs_body(const DS& d, u64* key_lds, u32 key_cap, u32* lds) {
     d.ctr->n_deliv = run;   // the saturating slot counter may have ended above deliv_max
   }
 }
+
+#include "dp_prio.h"   // k_prio_lane, k_prio_dispatch (DS.prio)
 
 // thread per delivery: expand its run (binary search), assign the channel's next delivery
 // tag, fill the unacked window slot, size the rendered frames

@@ -401,6 +401,18 @@ struct DS {
   u32* q_broom;             // [q_max] K_q of the step (k_byte_room): how many of the queue's pairs, in sort
                             // order, pass the reject-publish byte rule; written for the queues that have
                             // pairs and such a limit, read for no other
+
+  // ---------------- priority queues (x-max-priority; prio == 0: nothing below is read).  Read only by
+  // k_prio_lane, k_prio_dispatch and the PRIO instantiations of k_dequeue and k_dead_pack, which the
+  // engine launches with the option on.  A queue declared with x-max-priority P takes P + 1
+  // consecutive slots, its lanes: the base slot b holds priority P, slot b + k priority P - k, each an
+  // ordinary ring with its own head, tail, growth, TTL walk and requeue.  Bindings, consumers, q_rr
+  // and Basic.Get address the base slot; the lanes behind it have q_cons_n = 0.  Routing emits pairs
+  // for the base slot; k_prio_lane moves each to the lane of its publish's priority ahead of the
+  // sort, and k_prio_dispatch serves the base slot's consumers and Gets from the lanes in order
+  u32 prio;                 // kernel-uniform, like limits
+  u32* q_prio;              // [q_max] at a base slot P (1 .. PRIO_MAX), at every other slot 0
+  u32* q_lane_base;         // [q_max] for every lane, the base included, its base slot; else the slot itself
 };
 struct DlState {
   u32 dead_max;             // items of the dead list (<= DEAD_LIST_MAX)

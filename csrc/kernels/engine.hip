@@ -193,6 +193,9 @@ class Engine {
     // x-max-length-bytes honoured (q_blimit, q_bytes, q_broom; the BL instantiations and k_byte_room)
     d_.blimits = get("queue_limit_bytes", 0) ? 1u : 0u;
     if (d_.blimits && !d_.limits) throw std::runtime_error("queue_limit_bytes needs queue_limits");
+    // x-max-priority honoured (q_prio, q_lane_base; k_prio_lane, k_prio_dispatch and the PRIO instantiations)
+    d_.prio = get("priority_queues", 0) ? 1u : 0u;
+    if (d_.prio && d_.world > 1) throw std::runtime_error("priority_queues is not served on a sharded plane (world > 1)");
     d_.persist_max = d_.persist ? (u32)get("persist_max", d_.cmd_max) : 0;
     d_.persist_bytes = d_.persist ? get("persist_bytes", 64ull << 20) : 0;
     // restore / host-publish records at world 1: recovery batches (persist) and messages
@@ -511,6 +514,10 @@ class Engine {
       d_.q_blimit = (u64*)dev("q_blimit", 8ull * d_.q_max);
       d_.q_bytes = (u64*)dev("q_bytes", 8ull * d_.q_max);
       d_.q_broom = (u32*)dev("q_broom", 4ull * d_.q_max);
+    }
+    if (d_.prio) {
+      d_.q_prio = (u32*)dev("q_prio", 4ull * d_.q_max);
+      d_.q_lane_base = (u32*)dev("q_lane_base", 4ull * d_.q_max);
     }
     if (d_.dlx) {
       dl_h_.q_dlx = (u32*)dev("q_dlx", 4ull * d_.q_max);
@@ -1023,6 +1030,7 @@ class Engine {
     o["h2d_split_min"] = h2d_split_min_;
     o["queue_limits"] = d_.limits;
     o["queue_limit_bytes"] = d_.blimits;
+    o["priority_queues"] = d_.prio;
     o["dead_letter"] = d_.dlx; o["dead_max"] = dl_h_.dead_max; o["dead_bytes"] = dl_h_.dead_bytes; o["dead_room"] = dead_room_; o["x_death"] = dl_h_.xdeath;
     o["alternate_exchange"] = alt_ ? 1 : 0;
     o["persist"] = d_.persist; o["persist_max"] = d_.persist_max; o["persist_bytes"] = d_.persist_bytes;
@@ -2794,10 +2802,15 @@ class Engine {
   // enqueue, acks, dispatch, render (K7-K11)
   // dispatch = false (restore): enqueue only; nothing is delivered or rendered between
   // steps (the restored messages go out with the next step's dispatch)
-  void launch_tail(hipStream_t s, const DS& d, bool dispatch = true) {
+  // imp: the payload the imported publishes of this launch were read from (DS.prio: k_prio_lane reads
+  // their property bytes there; nullptr: DS.recv_pay)
+  void launch_tail(hipStream_t s, const DS& d, bool dispatch = true, const u8* imp = nullptr) {
     Range rg("chanamq.K7-K11.tail");
     u32 nch = d.c_max * d.chpc;
     const u32 pbits = d.q_bits + d.rank_bits;
+    // priority queues on (DS.prio): the pairs of priority queues move to their lanes ahead of the sort
+    if (d.prio)
+      hipLaunchKernelGGL(k_prio_lane, capped(ceil_div(d.pair_max, 256), 1024), dim3(256), 0, s, d, imp ? imp : d.recv_pay);
     if (pbits <= SORT_ONEPASS_BITS && !d.blimits) {
       // single-pass sort with the ring plan folded into the histogram's last block and the
       // enqueue into the scatter (k_rs_hist_plan / k_rs_scatter_enq): two launches
@@ -2840,6 +2853,15 @@ class Engine {
     else hipLaunchKernelGGL(k_chan_advance<false>, capped(nch, 1024), dim3(256), 0, s, d);
     // k_dequeue first puts requeued deliveries back in front of their queues' heads, in
     // queue-offset order (QueueEntity.scala:415-446), then dispatches
+    // (DS.prio: the PRIO instantiations leave the base slots of priority queues and the step's run
+    // layout to k_prio_dispatch, launched behind them)
+    if (d.prio) {
+      if (d.blimits && d.dlx) hipLaunchKernelGGL((k_dequeue<true, true, true>), dim3(d.q_max), dim3(256), 0, s, d);
+      else if (d.blimits) hipLaunchKernelGGL((k_dequeue<false, true, true>), dim3(d.q_max), dim3(256), 0, s, d);
+      else if (d.dlx) hipLaunchKernelGGL((k_dequeue<true, false, true>), dim3(d.q_max), dim3(256), 0, s, d);
+      else hipLaunchKernelGGL((k_dequeue<false, false, true>), dim3(d.q_max), dim3(256), 0, s, d);
+      hipLaunchKernelGGL(k_prio_dispatch, dim3(d.q_max), dim3(256), 0, s, d);
+    } else
     if (d.blimits && d.dlx) hipLaunchKernelGGL((k_dequeue<true, true>), dim3(d.q_max), dim3(256), 0, s, d);
     else if (d.blimits) hipLaunchKernelGGL((k_dequeue<false, true>), dim3(d.q_max), dim3(256), 0, s, d);
     else if (d.dlx) hipLaunchKernelGGL(k_dequeue<true>, dim3(d.q_max), dim3(256), 0, s, d);
@@ -2884,7 +2906,9 @@ class Engine {
     if (xd) {
       hipLaunchKernelGGL(k_dead_size, wave_blocks(dl_h_.dead_max), dim3(256), 0, s, d);
       hipLaunchKernelGGL(k_dead_pack<true>, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
-      hipLaunchKernelGGL(k_dead_pack<true>, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
+      // (DS.prio: the instantiation whose ban rows name a lane's base slot)
+      if (d.prio) hipLaunchKernelGGL((k_dead_pack<true, true>), wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
+      else hipLaunchKernelGGL(k_dead_pack<true>, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
     } else {
       hipLaunchKernelGGL(k_dead_pack<false>, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
       hipLaunchKernelGGL(k_dead_pack<false>, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
@@ -2908,7 +2932,7 @@ class Engine {
       launch_pack(s, d);
     } else {
       if (d.dlx) launch_dead(s, d);
-      launch_tail(s, d);
+      launch_tail(s, d, true, d.dlx ? dl_h_.dead_pay : nullptr);
     }
   }
 
@@ -2918,7 +2942,7 @@ class Engine {
   void launch_rest(hipStream_t s, const DS& d) {
     launch_route(s, d, d.pub_max);
     if (d.dlx) launch_dead(s, d);
-    launch_tail(s, d);
+    launch_tail(s, d, true, d.dlx ? dl_h_.dead_pay : nullptr);
   }
   // the launches f makes on stream st, captured once into *ge
   void capture(hipStream_t st, hipGraphExec_t* ge, const std::function<void()>& f) {
