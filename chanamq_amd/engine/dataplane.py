@@ -19,6 +19,7 @@ from .. import ops
 from ..protocol import constants as C
 from . import prio
 from .control import ControlError, ControlState
+from .features import Features
 from .layout import (CONN_OUT, CONSUMED_REC, EGRESS_REF, RING_MOVE, CTRL_REC, CTRL_DGET, CTRL_TXBUF, INVALID, MF_HAS_TS,
                      MF_HOSTPUB, MF_PERSIST,
                      MF_ONEQ, MF_REDELIVERED, MF_RESTORE,
@@ -72,45 +73,9 @@ class StepResult:
 
 class GpuDataPlane(ControlState):
     def __init__(self, device=0, hash_wildcard=True, graph=True, worker=0, default_queue_capacity=1 << 16,
-                 world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0,
-                 headers_match=False, queue_limits=False, dead_letter=False, x_death=False,
-                 alternate_exchange=False, queue_limit_bytes=False, priority_queues=False, **cfg):
-        """``priority_queues``: queues honour x-max-priority: a queue declared with P takes P + 1
-        consecutive slots, its lanes (q_prio / q_lane_base); k_prio_lane moves each routed pair to
-        the lane of its publish's priority ahead of the sort, and k_prio_dispatch, behind the PRIO
-        instantiation of k_dequeue, serves the base slot's consumers and Gets from the lanes in
-        order.  Off: the argument is ignored and the step launches what it launched before.
-        Single-rank planes only.
-
-        ``queue_limit_bytes`` (needs ``queue_limits``): queues honour x-max-length-bytes under
-        their x-overflow mode (q_blimit; the device keeps every queue's ready bytes in q_bytes:
-        k_byte_room and the BL instantiations of k_ring_plan / k_enqueue / k_dequeue / k_basic_get;
-        the step sorts its pairs on the materialised path at every key width).  Off: the argument
-        is ignored and the step launches what it launched before.
-
-        ``alternate_exchange``: Exchange.Declare's alternate-exchange argument is honoured: an
-        exchange the walk of route_one matched without any destination hands the publish to the
-        exchange it names (x_alt; the ALT instantiations of k_route / k_import_route; n_alt).  Off:
-        the argument is ignored and the step launches the instantiations without the rule.
-
-        ``x_death`` (needs ``dead_letter``): the dead pass rewrites each dead letter's property
-        bytes -- x-death / x-first-death-* headers, the expiration removed (k_dead_size,
-        k_dead_pack<true>: dp_xdeath.h) -- and its routing refuses the queues the history bans
-        (cycle detection; n_dl_cycle).  Off: the bytes are verbatim and the step's launches are
-        those of ``dead_letter`` alone.
-
-        ``dead_letter``: queues honour x-dead-letter-exchange / x-dead-letter-routing-key: entries
-        that expire, are trimmed by x-max-length or are rejected without requeue join the
-        device's dead list and are published to the exchange by the next step's dead pass
-        (k_dead_pack; engine cfg dead_max / dead_bytes bound the list and one pass's payload).
-        Off: the device never reads the fields.  Single-rank planes only.
-
-        ``queue_limits``: queues honour x-max-length / x-overflow (q_limit: trim_head in
-        k_dequeue, the refusal in enq_store).  Off: the device never reads the field.
-
-        ``headers_match``: headers exchanges match on their bindings' arguments (the
-        headers branch of route_one; engine cfg hb_max / hp_max bound its tables).  Off: they
-        route as topic.
+                 world=1, rank=0, shard_map=None, exchanger=None, exchange_lag=0, egress_ref=0, **cfg):
+        """The opt-in features (``queue_limits=True``, ...: features.TABLE describes each) are taken
+        out of ``cfg``; what is left is the engine's cfg.
 
         ``egress_ref``: egress by reference -- a delivery whose body arrived in the
         ingress payload of the same step (or up to ``egress_ref`` steps earlier) is rendered
@@ -118,14 +83,7 @@ class GpuDataPlane(ControlState):
         splice it back in; the native front end sends it with sendmsg iovecs).  The caller
         keeps each payload unchanged until the delivering step's egress is collected
         (``step()`` does: a payload buffer is reused two steps later).  None / -1: off."""
-        if dead_letter and world > 1:
-            raise ValueError("dead_letter=True is not served on a sharded plane (world > 1)")
-        if x_death and not dead_letter:
-            raise ValueError("x_death=True needs dead_letter=True")
-        if queue_limit_bytes and not queue_limits:
-            raise ValueError("queue_limit_bytes=True needs queue_limits=True")
-        if priority_queues and world > 1:
-            raise ValueError("priority_queues=True is not served on a sharded plane (world > 1)")
+        feats = Features.take(cfg).validate(world)
         self.mod = ops.load()
         full = dict(cfg)
         full.setdefault("egress_ref_back", -1 if egress_ref is None else int(egress_ref))
@@ -143,13 +101,7 @@ class GpuDataPlane(ControlState):
             full.setdefault("overlap", 0)
             full.setdefault("copy_engine", 3)
         full.update(device=device, hash_wildcard=int(hash_wildcard), graph=int(graph), world=world, rank=rank,
-                    exchange_lag=int(exchange_lag), queue_limits=int(bool(queue_limits)),
-                    dead_letter=int(bool(dead_letter)), x_death=int(bool(x_death)),
-                    alternate_exchange=int(bool(alternate_exchange)))
-        if queue_limit_bytes:   # (off: the engine's cfg is what it was)
-            full.update(queue_limit_bytes=1)
-        if priority_queues:
-            full.update(priority_queues=1)
+                    exchange_lag=int(exchange_lag), **feats.engine_cfg())
         self.eng = self.mod.Engine(full)
         self.info = self.eng.info()
         sz = self.info["sizeof"]
@@ -204,9 +156,7 @@ class GpuDataPlane(ControlState):
         super().__init__(c_max=i["c_max"], chpc=i["chpc"], q_max=i["q_max"], x_max=i["x_max"],
                          cons_max=i["cons_max"], hash_wildcard=hash_wildcard, ring_pool=i["ring_pool"],
                          default_queue_capacity=default_queue_capacity, world=world, rank=rank,
-                         shard_map=shard_map, headers_match=headers_match, queue_limits=queue_limits,
-                         dead_letter=dead_letter, x_death=x_death, alternate_exchange=alternate_exchange,
-                         queue_limit_bytes=queue_limit_bytes, priority_queues=priority_queues)
+                         shard_map=shard_map, features=feats)
         # (a durable priority queue is refused where a store takes the plane's records: control.py)
         self.persist = bool(i.get("persist"))
         if self.priority_queues:   # every slot is its own base until a priority queue takes it

@@ -38,6 +38,7 @@ import uuid
 import numpy as np
 
 from ..engine.control import ControlError, normalize_vhost
+from ..engine.features import BY_NAME, Features
 from ..engine.layout import MF_HAS_TS, MF_PERSIST, SS_FRAME_ERROR, SS_OVERFLOW, SS_TOO_LARGE, SS_UNEXPECTED
 from ..protocol import constants as C
 from ..protocol.codec import (Method, Typed, decode_content_header, decode_method, encode_method_frame, encode_table,
@@ -219,9 +220,7 @@ class GpuBroker:
                  ingress_bytes=64 << 20, per_conn_read=256 << 10, mem_high_watermark=None, mem_low_watermark=None,
                  store=None, node=None, reuseport=False, io_threads=4, fe_cfg=None, spill_at=None, spill_hot=1024,
                  confirm_read=128 << 10, cold_dir=None, cold=True, cold_hot=1 << 16, cold_window=1 << 15, cold_beside=True,
-                 persist_group_ms=2.0, exchange_bindings=False, headers_match=False, queue_limits=False,
-                 dead_letter=False, x_death=False, alternate_exchange=False, queue_limit_bytes=False,
-                 priority_queues=False):
+                 persist_group_ms=2.0, exchange_bindings=False, **features):
         """``io``: "pipeline" = native pipelined front end (csrc/core/frontend.cpp: IO
         threads + a stepper thread keeping two steps in flight, no Python per step),
         "native" = C++ batched gateway polled by a Python step loop (csrc/core/
@@ -231,55 +230,20 @@ class GpuBroker:
         # Exchange.Bind / Exchange.Unbind (exchange-to-exchange bindings, routed by the data
         # plane's closure walk): served and advertised when on, 540 NOT_IMPLEMENTED when off
         self.exchange_bindings = bool(exchange_bindings)
-        # headers exchanges matched on their bindings' arguments (chana.mq.gpu.headers-match):
-        # the plane does the matching (built with headers_match=True); the broker passes
-        # Queue.Bind / Queue.Unbind (and Exchange.Bind / Unbind) arguments on only when it is on
-        self.headers_match = bool(headers_match)
-        if self.headers_match and not getattr(plane, "headers_match", False):
-            raise ValueError("headers_match=True needs a data plane built with headers_match=True")
-        # queue length limits (chana.mq.gpu.queue-limits): Queue.Declare's x-max-length / x-overflow
-        # are parsed and passed to the plane (built with queue_limits=True, which enforces them);
-        # off, they are ignored as always before
-        self.queue_limits = bool(queue_limits)
-        if self.queue_limits and not getattr(plane, "queue_limits", False):
-            raise ValueError("queue_limits=True needs a data plane built with queue_limits=True")
-        # byte limits (chana.mq.gpu.queue-limit-bytes): Queue.Declare's x-max-length-bytes is parsed
-        # and passed to the plane (built with queue_limit_bytes=True), under the queue's x-overflow
-        # mode; off, it is ignored as always before
-        self.queue_limit_bytes = bool(queue_limit_bytes)
-        if self.queue_limit_bytes and not self.queue_limits:
-            raise ValueError("queue_limit_bytes=True needs queue_limits=True")
-        if self.queue_limit_bytes and not getattr(plane, "queue_limit_bytes", False):
-            raise ValueError("queue_limit_bytes=True needs a data plane built with queue_limit_bytes=True")
-        # priority queues (chana.mq.gpu.priority-queues): Queue.Declare's x-max-priority is parsed and
-        # passed to the plane (built with priority_queues=True, which serves it); off, it is ignored
-        # as always before.  Single node only
-        self.priority_queues = bool(priority_queues)
-        if self.priority_queues and not getattr(plane, "priority_queues", False):
-            raise ValueError("priority_queues=True needs a data plane built with priority_queues=True")
-        if self.priority_queues and node is not None:
-            raise ValueError("priority_queues=True is not served on a sharded node")
-        # dead-lettering (chana.mq.gpu.dead-letter): Queue.Declare's x-dead-letter-exchange /
-        # x-dead-letter-routing-key are parsed and passed to the plane (built with dead_letter=True,
-        # which serves them); off, they are ignored as always before.  Single node only
-        self.dead_letter = bool(dead_letter)
-        if self.dead_letter and not getattr(plane, "dead_letter", False):
-            raise ValueError("dead_letter=True needs a data plane built with dead_letter=True")
-        if self.dead_letter and node is not None:
-            raise ValueError("dead_letter=True is not served on a sharded node")
-        # x-death headers and cycle detection (chana.mq.gpu.dead-letter-x-death): the plane's work
-        # (built with x_death=True); here only the dl_cycle statistic
-        self.x_death = bool(x_death)
-        if self.x_death and not self.dead_letter:
-            raise ValueError("x_death=True needs dead_letter=True")
-        if self.x_death and not getattr(plane, "x_death", False):
-            raise ValueError("x_death=True needs a data plane built with x_death=True")
-        # alternate exchanges (chana.mq.gpu.alternate-exchange): the plane's work (built with
-        # alternate_exchange=True: Exchange.Declare's argument is validated, kept and routed by);
-        # here the alt_routed statistic, and the argument's check in front of a sharded declare
-        self.alternate_exchange = bool(alternate_exchange)
-        if self.alternate_exchange and not getattr(plane, "alternate_exchange", False):
-            raise ValueError("alternate_exchange=True needs a data plane built with alternate_exchange=True")
+        # the opt-in features (engine/features.py TABLE: headers_match=True, ...), each a plain
+        # attribute too.  One that is on needs a plane built with it; one that is off may sit
+        # over a plane that has it on
+        self.features = Features.take(features)
+        if features:
+            raise TypeError(f"GpuBroker.__init__() got an unexpected keyword argument {next(iter(features))!r}")
+        vars(self).update(self.features.asdict())
+        for f in self.features.on():
+            if f.requires and not getattr(self, f.requires):
+                raise ValueError(f"{f.name}=True needs {f.requires}=True")
+            if not getattr(plane, f.name, False):
+                raise ValueError(f"{f.name}=True needs a data plane built with {f.name}=True")
+            if f.single_rank and node is not None:
+                raise ValueError(f"{f.name}=True is not served on a sharded node")
         native_x = bool(getattr(plane, "native_xchg", False))
         if io == "auto":
             io = "pipeline" if (hasattr(plane, "eng") and (node is None or native_x)) else "native"
@@ -388,14 +352,7 @@ class GpuBroker:
         self._running = False
         self._wake_r, self._wake_w = os.pipe()
         self.stats = dict(steps=0, published=0, delivered=0, connections=0)
-        if self.queue_limits:
-            self.stats.update(maxlen_dropped=0, maxlen_rejected=0)
-        if self.dead_letter:
-            self.stats.update(dict.fromkeys(self.DL_STATS, 0))
-        if self.x_death:
-            self.stats["dl_cycle"] = 0
-        if self.alternate_exchange:
-            self.stats["alt_routed"] = 0
+        self._feature_stats()
         self.lock = _PlaneLock(self)
         self.light = _LightLock(self.lock)
 
@@ -864,14 +821,7 @@ class GpuBroker:
             return
         st = self.fe.stats()
         self.stats.update(steps=st["steps"], published=st["published"], delivered=st["delivered"])
-        if self.queue_limits:
-            self.stats.update(maxlen_dropped=st.get("maxlen_dropped", 0), maxlen_rejected=st.get("maxlen_rejected", 0))
-        if self.dead_letter:
-            self.stats.update({k: st.get(k, 0) for k in self.DL_STATS})
-        if self.x_death:
-            self.stats["dl_cycle"] = st.get("dl_cycle", 0)
-        if self.alternate_exchange:
-            self.stats["alt_routed"] = st.get("alt_routed", 0)
+        self._feature_stats(st)
         if st.get("spill_moved"):
             self.stats["spilled_bytes"] = st["spill_moved"]
         self._fe_stats = st
@@ -1294,17 +1244,7 @@ class GpuBroker:
         self.stats["steps"] += 1
         self.stats["published"] += cnt.get("n_pubs", 0)
         self.stats["delivered"] += cnt.get("n_deliv", 0)
-        if self.queue_limits:   # x-max-length: trimmed from drop-head queues / refused by reject-publish queues
-            self.stats["maxlen_dropped"] += cnt.get("n_maxlen_dropped", 0)
-            self.stats["maxlen_rejected"] += cnt.get("n_maxlen_rejected", 0)
-        if self.dead_letter:   # dead-lettered by reason, dead letters lost, entries pending on the device's list
-            for k in self.DL_STATS[:-1]:
-                self.stats[k] += cnt.get("n_" + k, 0)
-            self.stats["dl_pending"] = cnt.get("n_dl_pending", 0)
-        if self.x_death:   # (dead letter, queue) pairs refused: the queue is in the dead letter's own history
-            self.stats["dl_cycle"] += cnt.get("n_dl_cycle", 0)
-        if self.alternate_exchange:   # (publish, exchange) pairs whose alternate exchange was taken
-            self.stats["alt_routed"] += cnt.get("n_alt", 0)
+        self._feature_stats(cnt, step=True)
         for conn, code, chslot in events:
             c = self.conns.get(conn)
             if c is None or c.state != "open":
@@ -1564,7 +1504,15 @@ class GpuBroker:
         expire_ms = now + int(exp) if isinstance(exp, str) and exp.isdigit() else 0
         return now, flags, expire_ms, ts_ms
 
-    DL_STATS = ("dl_expired", "dl_maxlen", "dl_rejected", "dl_unrouted", "dl_dropped", "dl_pending")
+    DL_STATS = tuple(s[0] for s in BY_NAME["dead_letter"].stats)
+
+    def _feature_stats(self, src={}, step=False):
+        """The statistics of the features that are on: zeroed; set from the front end's
+        statistics (keyed as ours); or, ``step``, advanced by a step's counters (gauges set)."""
+        for f in self.features.on():
+            for stat, counter, gauge in f.stats:
+                v = src.get(counter if step else stat, 0)
+                self.stats[stat] = v + self.stats[stat] if step and not gauge else v
 
     def _dlx_args(self, m):
         """Queue.Declare's x-dead-letter-exchange / x-dead-letter-routing-key as ``declare_queue``

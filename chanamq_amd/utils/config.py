@@ -11,6 +11,8 @@ import json
 import os
 import re
 
+from ..engine.features import Features
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REFERENCE_CONF = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "conf", "reference.conf")
 
@@ -282,40 +284,9 @@ class Config:
         if store_dir:
             plane.update(persist=1, persist_max=int(g(k + "persist-records", 1 << 16)),
                          persist_bytes=int(g(k + "persist-bytes", 256 << 20)))
-        # headers exchanges matched on their bindings' arguments (off: they route as topic);
-        # headers-bindings / headers-pairs bound the device's row table and pair pool
-        headers_match = bool(g(k + "headers-match", False))
-        if headers_match:
-            hb = int(g(k + "headers-bindings", 1024))
-            plane.update(headers_match=True, hb_max=hb, hp_max=int(g(k + "headers-pairs", 4 * hb)))
-        # queues honour Queue.Declare's x-max-length / x-overflow (off: the arguments are ignored)
-        queue_limits = bool(g(k + "queue-limits", False))
-        if queue_limits:
-            plane.update(queue_limits=True)
-        # queues honour Queue.Declare's x-max-length-bytes under their x-overflow mode (needs queue-limits)
-        queue_limit_bytes = bool(g(k + "queue-limit-bytes", False))
-        if queue_limit_bytes:
-            if not queue_limits:
-                raise ValueError("chana.mq.gpu.queue-limit-bytes needs chana.mq.gpu.queue-limits")
-            plane.update(queue_limit_bytes=True)
-        # queues honour Queue.Declare's x-max-priority (off: the argument is ignored).  Single node only
-        priority_queues = bool(g(k + "priority-queues", False))
-        if priority_queues:
-            plane.update(priority_queues=True)
-        # queues honour Queue.Declare's x-dead-letter-exchange / x-dead-letter-routing-key (off: ignored)
-        dead_letter = bool(g(k + "dead-letter", False))
-        if dead_letter:
-            plane.update(dead_letter=True, dead_max=int(g(k + "dead-max", 1024)), dead_bytes=int(g(k + "dead-bytes", 8 << 20)))
-        # dead letters carry x-death / x-first-death-* headers and cycles are refused (needs dead-letter)
-        x_death = bool(g(k + "dead-letter-x-death", False))
-        if x_death:
-            if not dead_letter:
-                raise ValueError("chana.mq.gpu.dead-letter-x-death needs chana.mq.gpu.dead-letter")
-            plane.update(x_death=True)
-        # Exchange.Declare's alternate-exchange is honoured (off: the argument is ignored)
-        alternate_exchange = bool(g(k + "alternate-exchange", False))
-        if alternate_exchange:
-            plane.update(alternate_exchange=True)
+        # the opt-in features and the sizes that ride with them (engine/features.py has the keys)
+        feats, on = Features.from_config(g, k)
+        plane.update(on)
         hi = int(g("chana.mq.flow.memory-high-watermark", -1))
         lo = int(g("chana.mq.flow.memory-low-watermark", -1))
         if hi < 0:   # 40% of what the broker can hold: the HBM body log + the host spill ring
@@ -327,9 +298,7 @@ class Config:
                       confirm_read=int(g(k + "confirm-read", 128 << 10)),
                       persist_group_ms=float(g(k + "persist-group-ms", 2.0)),
                       exchange_bindings=bool(g(k + "exchange-bindings", False)),
-                      headers_match=headers_match, queue_limits=queue_limits, dead_letter=dead_letter, x_death=x_death,
-                      alternate_exchange=alternate_exchange, queue_limit_bytes=queue_limit_bytes,
-                      priority_queues=priority_queues, mem_high_watermark=hi, mem_low_watermark=lo)
+                      mem_high_watermark=hi, mem_low_watermark=lo, **feats.asdict())
         return plane, broker
 
     def __repr__(self):

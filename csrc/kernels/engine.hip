@@ -2572,12 +2572,10 @@ class Engine {
     Range rg("chanamq.basic_get");
     sync();
     const u32 last = (u32)(seq_ ? seq_ - 1 : 0);   // (the last step submitted; before the first: 0)
-    if (d_.blimits)
-      hipLaunchKernelGGL(k_basic_get<true>, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms,
+    with_flags([&](auto BL) {
+      hipLaunchKernelGGL(k_basic_get<BL()>, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms,
                          get_out_dev_, get_cap_, get_res_dev_, last);
-    else
-      hipLaunchKernelGGL(k_basic_get<false>, dim3(1), dim3(64), 0, s_comp_, par_[0].io, q, chslot, noack, now_ms,
-                         get_out_dev_, get_cap_, get_res_dev_, last);
+    }, d_.blimits != 0);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s_comp_));
     const GetRes& r = *get_res_h_;
@@ -2714,6 +2712,15 @@ class Engine {
     else if (bits == 10) f(std::integral_constant<u32, 10>{});
     else f(std::integral_constant<u32, 11>{});
   }
+  // f(std::bool_constant<B0>{}, std::bool_constant<B1>{}, ...) for the runtime booleans b0, b1, ...:
+  // the launch of the kernel instantiation a combination of options selects, written once
+  template <class F>
+  static void with_flags(F&& f) { f(); }
+  template <class F, class... B>
+  static void with_flags(F&& f, bool b, B... rest) {
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+  }
   // returns index (0/1) of the buffer holding the sorted output
   u32 radix_sort(hipStream_t s, const DS& d, u32** keys, u32** vals, const u32* n, u32 nmax, u32 bits) {
     const u32 ntiles = ceil_div(nmax, SORT_TILE);
@@ -2771,12 +2778,10 @@ class Engine {
     // the idle blocks of a capacity-sized grid were still dispatched after the busy ones
     const u64 ngroups = ceil_div(nmax ? nmax : 1, 16);
     // (alt_: the instantiations with the alternate-exchange rule, launched only with the option on)
-    if (imports && ban && alt_) hipLaunchKernelGGL((k_import_route<true, true>), capped(ngroups, n_cu_), dim3(1024), 0, s, d);
-    else if (imports && ban) hipLaunchKernelGGL(k_import_route<true>, capped(ngroups, n_cu_), dim3(1024), 0, s, d);
-    else if (imports && alt_) hipLaunchKernelGGL((k_import_route<false, true>), capped(ngroups, n_cu_), dim3(1024), 0, s, d);
-    else if (imports) hipLaunchKernelGGL(k_import_route<false>, capped(ngroups, n_cu_), dim3(1024), 0, s, d);   // + prep, link acks
-    else if (alt_) hipLaunchKernelGGL(k_route<true>, capped(ngroups, 2 * n_cu_), dim3(1024), 0, s, d);
-    else hipLaunchKernelGGL(k_route<false>, capped(ngroups, 2 * n_cu_), dim3(1024), 0, s, d);
+    with_flags([&](auto BAN, auto ALT) {
+      if (imports) hipLaunchKernelGGL((k_import_route<BAN(), ALT()>), capped(ngroups, n_cu_), dim3(1024), 0, s, d);   // + prep, link acks
+      else hipLaunchKernelGGL(k_route<ALT()>, capped(ngroups, 2 * n_cu_), dim3(1024), 0, s, d);
+    }, ban, alt_);
     // scan of the routing counts + the phase's log reservation, then pairs + store
     const ScanArgs a = scan_args({{d.pub_nq, d.pub_pair_off}, {d.pub_slot, d.pub_slot_off},
                                   {d.pub_routed, d.pub_routed_rank}, {d.pub_ret_sz, d.pub_ret_off}},
@@ -2831,14 +2836,11 @@ class Engine {
       // arrays, which the fused path never materialises -- with K_q computed ahead of the ring plan
       // and the BL instantiations of the plan and the enqueue
       const dim3 pg = capped(ceil_div(d.pair_max, 256), 1024);
-      if (d.blimits) {
-        hipLaunchKernelGGL(k_byte_room, pg, dim3(256), 0, s, d, psrc);
-        hipLaunchKernelGGL(k_ring_plan<true>, pg, dim3(256), 0, s, d, psrc);
-        hipLaunchKernelGGL(k_enqueue<true>, pg, dim3(256), 0, s, d, psrc);
-      } else {
-        hipLaunchKernelGGL(k_ring_plan<false>, pg, dim3(256), 0, s, d, psrc);
-        hipLaunchKernelGGL(k_enqueue<false>, pg, dim3(256), 0, s, d, psrc);
-      }
+      if (d.blimits) hipLaunchKernelGGL(k_byte_room, pg, dim3(256), 0, s, d, psrc);
+      with_flags([&](auto BL) {
+        hipLaunchKernelGGL(k_ring_plan<BL()>, pg, dim3(256), 0, s, d, psrc);
+        hipLaunchKernelGGL(k_enqueue<BL()>, pg, dim3(256), 0, s, d, psrc);
+      }, d.blimits != 0);
     }
     // without persistence nothing runs after k_post: it also writes the host-visible
     // outputs and its last block the counters (fused k_host_out)
@@ -2849,23 +2851,15 @@ class Engine {
       if (!fin) hipLaunchKernelGGL(k_host_out, dim3(64), dim3(256), 0, s, d);
       return;
     }
-    if (d.dlx) hipLaunchKernelGGL(k_chan_advance<true>, capped(nch, 1024), dim3(256), 0, s, d);
-    else hipLaunchKernelGGL(k_chan_advance<false>, capped(nch, 1024), dim3(256), 0, s, d);
     // k_dequeue first puts requeued deliveries back in front of their queues' heads, in
-    // queue-offset order (QueueEntity.scala:415-446), then dispatches
+    // queue-offset order (QueueEntity.scala:415-446), then dispatches; its last block lays out the runs
     // (DS.prio: the PRIO instantiations leave the base slots of priority queues and the step's run
     // layout to k_prio_dispatch, launched behind them)
-    if (d.prio) {
-      if (d.blimits && d.dlx) hipLaunchKernelGGL((k_dequeue<true, true, true>), dim3(d.q_max), dim3(256), 0, s, d);
-      else if (d.blimits) hipLaunchKernelGGL((k_dequeue<false, true, true>), dim3(d.q_max), dim3(256), 0, s, d);
-      else if (d.dlx) hipLaunchKernelGGL((k_dequeue<true, false, true>), dim3(d.q_max), dim3(256), 0, s, d);
-      else hipLaunchKernelGGL((k_dequeue<false, false, true>), dim3(d.q_max), dim3(256), 0, s, d);
-      hipLaunchKernelGGL(k_prio_dispatch, dim3(d.q_max), dim3(256), 0, s, d);
-    } else
-    if (d.blimits && d.dlx) hipLaunchKernelGGL((k_dequeue<true, true>), dim3(d.q_max), dim3(256), 0, s, d);
-    else if (d.blimits) hipLaunchKernelGGL((k_dequeue<false, true>), dim3(d.q_max), dim3(256), 0, s, d);
-    else if (d.dlx) hipLaunchKernelGGL(k_dequeue<true>, dim3(d.q_max), dim3(256), 0, s, d);
-    else hipLaunchKernelGGL(k_dequeue<false>, dim3(d.q_max), dim3(256), 0, s, d);   // (its last block lays out the runs)
+    with_flags([&](auto DLX, auto BL, auto PRIO) {
+      hipLaunchKernelGGL(k_chan_advance<DLX()>, capped(nch, 1024), dim3(256), 0, s, d);
+      hipLaunchKernelGGL((k_dequeue<DLX(), BL(), PRIO()>), dim3(d.q_max), dim3(256), 0, s, d);
+    }, d.dlx != 0, d.blimits != 0, d.prio != 0);
+    if (d.prio) hipLaunchKernelGGL(k_prio_dispatch, dim3(d.q_max), dim3(256), 0, s, d);
     hipLaunchKernelGGL(k_dv_write, blocks(d.deliv_max, 256), dim3(256), 0, s, d);
     if (d.c_max <= CONN_LAYOUT_MAX) {
       hipLaunchKernelGGL(k_conn_layout, dim3(1), dim3(1024), 0, s, d);   // + the delivery-size scan
@@ -2903,16 +2897,12 @@ class Engine {
     // x-death: one launch more, the pending items' new property lengths, before phase 0 takes its
     // prefix by them; phase 1 then rewrites the bytes and fills the ban rows the routing reads
     const bool xd = dl_h_.xdeath != 0;
-    if (xd) {
-      hipLaunchKernelGGL(k_dead_size, wave_blocks(dl_h_.dead_max), dim3(256), 0, s, d);
-      hipLaunchKernelGGL(k_dead_pack<true>, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
-      // (DS.prio: the instantiation whose ban rows name a lane's base slot)
-      if (d.prio) hipLaunchKernelGGL((k_dead_pack<true, true>), wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
-      else hipLaunchKernelGGL(k_dead_pack<true>, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
-    } else {
-      hipLaunchKernelGGL(k_dead_pack<false>, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
-      hipLaunchKernelGGL(k_dead_pack<false>, wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
-    }
+    if (xd) hipLaunchKernelGGL(k_dead_size, wave_blocks(dl_h_.dead_max), dim3(256), 0, s, d);
+    with_flags([&](auto XD, auto PRIO) {
+      hipLaunchKernelGGL(k_dead_pack<XD()>, dim3(1), dim3(1024), 0, s, d, 0u, dead_room_);
+      // (x-death with DS.prio: the instantiation whose ban rows name a lane's base slot)
+      hipLaunchKernelGGL((k_dead_pack<XD(), XD() && PRIO()>), wave_blocks(dead_room_), dim3(256), 0, s, d, 1u, dead_room_);
+    }, xd, d.prio != 0);
     DS v = d;
     v.dlx = 2;
     v.recv_desc = dl_h_.dead_desc;
